@@ -17,6 +17,13 @@ RCCL over xGMI) and every rank draws the identical Gamma update.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for the
 roofline and cpu_baseline fields).
+
+A plain run sets up, warms up, times the steps and prints the line.  The
+side measurements (the UNIF sampler, weak scaling, the two CPU baselines)
+take runs of their own and are made only with ``--full``.
+``--dump-outputs DIR`` writes what the timed call returned (the chain's
+draws) as DIR/<name>.npy; data, priors, seeds and hence the draws are the
+same from run to run with the same arguments.
 """
 from __future__ import annotations
 
@@ -75,6 +82,16 @@ def cpu_baseline(n, y, cen, T, nu, zeta, method=2, target_s=15.0):
                       f"single thread of the GPU box's host CPU"}
 
 
+def dump_outputs(path, res):
+    """What the timed Sweeper.gibbs call returned, as float64 .npy files:
+    draws.npy [steps + 1, m] (row 0 = the start the warm-up left, row k = the
+    parameters drawn by timed sweep k) and last_draw.npy [m], its last row."""
+    os.makedirs(path, exist_ok=True)
+    res = np.ascontiguousarray(res, np.float64)
+    np.save(os.path.join(path, "draws.npy"), res)
+    np.save(os.path.join(path, "last_draw.npy"), res[-1])
+
+
 def load_counters(path, n, n_local, method, lib_key):
     """PMC counters of profiles/traffic_latest.json for this workload, or
     (None, None, reason).  Fail closed: the file must name the sha256 of the
@@ -104,9 +121,14 @@ def main():
     ap.add_argument("--N", "--obs", dest="N", type=int, default=1_000_000)
     ap.add_argument("--method", default="ECS", choices=["ECS", "MHRS", "DCS", "UNIF"])
     ap.add_argument("--censor", type=float, default=0.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling side measurement (N > 1)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the UNIF side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also make the side measurements (UNIF sampler, weak scaling, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the draws of the timed steps as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-weak", action="store_true",
+                    help="with --full: skip the weak-scaling side measurement (N > 1)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the UNIF side measurement")
     ap.add_argument("--traffic-file", default=os.path.join(REPO, "profiles", "traffic_latest.json"))
     args = ap.parse_args()
 
@@ -204,6 +226,8 @@ def main():
     if not np.all(np.isfinite(res)):
         raise SystemExit("non-finite Gibbs draws")
     sw.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # Side measurement (not `value`): the same workload through the opt-in
     # uniformisation sampler (method 8, pht_unif.h), which samples the same
@@ -211,7 +235,7 @@ def main():
     # the reference's ECS chains (tests/test_gpu_posterior.py).  `value`
     # stays the reference's own sampler.
     alt = None
-    if args.method == "ECS" and not args.no_alt:
+    if args.full and args.method == "ECS" and not args.no_alt:
         sw3 = P.Sweeper(n, P.METHODS["UNIF"], 1, device=local)
         sw3.set_obs(y[lo:hi], cen[lo:hi], obs0=lo)
         sw3.set_global_count(N)
@@ -243,7 +267,7 @@ def main():
                                         "chains. `value` is the reference's default ECS sampler"}
 
     weak = None
-    if dist is not None and not args.no_weak:
+    if args.full and dist is not None and not args.no_weak:
         # Side measurement (not `value`): weak scaling, every rank holding N
         # observations of its own (one chain over world x N observations).
         yw, cw = simulate_ph(S, s, N, seed=DATA_KEY + 1 + rank, censor_frac=args.censor)
@@ -312,7 +336,7 @@ def main():
             line["alt_sampler"] = alt
         if weak is not None:
             line["weak_scaling"] = weak
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # UNIF has no reference counterpart: its CPU baseline is the
             # reference's own sampler for the same workload, ECS
             cpu_method = method if method in (1, 2, 4) else 2

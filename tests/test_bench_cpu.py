@@ -28,6 +28,7 @@ def test_bench_help():
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert p.returncode == 0 and "--no-cpu-baseline" in p.stdout
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
 
 
 def test_counters_fail_closed(tmp_path):

@@ -37,7 +37,7 @@ def test_bench_under_torchrun_rccl(gpu, reduce_at_world1):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-           "--N", "200000", "--no-cpu-baseline"]
+           "--N", "200000", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, PHT_WORLD1_REDUCE="1" if reduce_at_world1 else "0")
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

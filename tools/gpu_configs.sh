@@ -9,7 +9,7 @@ TAG=${1:-cfgs}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-run() { local name=$1; shift; timeout -k 10 240 python3 bench.py --no-cpu-baseline "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; exit 1; }; echo "$name ok"; }
+run() { local name=$1; shift; timeout -k 10 240 python3 bench.py --full --no-cpu-baseline "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; exit 1; }; echo "$name ok"; }
 run cfg1_ecs --n 3 --N 200 --steps 1000
 run cfg2_ecs --n 5 --N 10000 --steps 50
 run cfg3_ecs --n 20 --N 100000 --steps 20

@@ -13,7 +13,7 @@ timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1 
 echo "gpu tests ok"
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; exit 1; }
 echo "smoke ok"
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
 echo "bench ok"
 bash tools/prof_trace.sh $TAG --steps 10 || { echo "trace failed"; exit 1; }
 echo "trace ok"

@@ -7,7 +7,8 @@
 #   tests=<pytest args>      python -m pytest -m gpu <args>  (e.g. tests=tests/test_gpu_fullsize.py)
 #   allgpu                   the whole -m gpu suite
 #   smoke                    __graft_entry__.smoke()
-#   bench=<bench.py args>    one bench line -> bench_<k>.json (k = step index)
+#   bench=<bench.py args>    one bench line -> bench_<k>.json (k = step index); pass --full for the
+#                            side measurements (UNIF sampler, weak scaling, CPU baselines)
 #   shards=<W>               tools/latency.py --shards W -> shards_W.jsonl
 #   latency=<args>           tools/latency.py <args> -> latency_<k>.jsonl
 #   trace=<bench args>       rocprofv3 kernel trace of bench.py (tools/prof_trace.sh)
