@@ -147,6 +147,41 @@ int pht_gibbs_run_chains(pht_ctx **ctxs, int nchains, const uint32_t *seeds, int
                          const double *nu, const double *zeta, const int *T, const double *C, int zexp,
                          const double *start, double *res, double *kernel_ms_max);
 
+/* ---- log-likelihood of posterior draws -------------------------------------
+ * No reference counterpart (the reference returns the draws only).  The
+ * observed-data log-likelihood of draw theta -> (S, s), pi = e_1:
+ *   sum over exact y of log f(y) + sum over censored y of log Fbar(y),
+ * evaluated on the GPU from the draw's eigensystem over the context's resident
+ * observations; arithmetic and layouts are specified in include/pht_loglik.h.
+ * SPECTRAL ONLY: a draw whose spectrum is complex or defective (dgeevx info,
+ * a non-zero imaginary part, a non-finite coefficient) gets a non-zero flag
+ * word, is never evaluated, and reads NaN.
+ *
+ * pht_loglik_build: host only (no GPU), one draw's block of pht_loglik_bytes(n)
+ *   bytes; returns 0, the positive flag word of an unusable draw, < 0 on error.
+ * pht_theta_to_S: one row of the chain -> (S, s) (column-major n x n, n), with
+ *   the T / C maps of pht_gibbs_run and the diagonal order of its update.
+ * pht_ctx_loglik: ndraws blocks, `batch` (1..64) per launch, on the context's
+ *   stream; any method's context; fails (no launch) without observations.
+ *   totals: 4 int64 words per draw [H, F, nbad, nobs]: the draw's
+ *   log-likelihood is H + F 2^-32 over its nobs good observations (exact
+ *   integer sums: independent of batch, grid and shard, and summed across
+ *   ranks like the statistics block); nbad observations had a non-positive or
+ *   non-finite density and are left out.  All four stay 0 for a flagged draw.
+ *   pointwise: NULL, or ndraws * count values l[d * count + i] in the caller's
+ *   observation order (NaN where bad or flagged).  accumulate != 0: the
+ *   per-observation WAIC state (pht_waic_t) takes every finite l, in draw order.
+ *   pht_ctx_last_kernel_ms then gives the device time of the call's launches.
+ * pht_ctx_loglik_reset zeroes that state; pht_ctx_loglik_state copies it out
+ *   in the caller's observation order (count values each). */
+int pht_loglik_bytes(int n);
+int pht_loglik_build(int n, const double *S, const double *s, unsigned char *out, int out_bytes);
+int pht_theta_to_S(int n, int m, const int *T, const double *C, const double *theta, double *S, double *s);
+int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
+                   double *pointwise, int accumulate);
+int pht_ctx_loglik_reset(pht_ctx *c);
+int pht_ctx_loglik_state(pht_ctx *c, double *ref, double *S1, double *S2, double *m, double *r, int *cnt);
+
 #ifdef __cplusplus
 }
 #endif

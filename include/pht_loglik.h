@@ -1,0 +1,110 @@
+/*
+ * pht_loglik.h — specification of the observed-data log-likelihood of a
+ * posterior draw, shared by the HIP kernel (phasetype_amd/csrc/pht_loglik.hip),
+ * the host (gibbs_host.cpp) and the tests' CPU restatement
+ * (tests/loglik_spec.c).
+ *
+ * For a draw theta -> (S, s) with S = Q diag(lambda) Q^-1 and pi = e_1 (as in
+ * every kernel here, src/PHT_MCMC_Aslett.c:279-297):
+ *   exact observation     f(y)    = pi exp(S y) s = sum_i a_i exp(lambda_i y)
+ *   censored observation  Fbar(y) = pi exp(S y) 1 = sum_i b_i exp(lambda_i y)
+ *   a_i = piQ_i (Q^-1 s)_i,  b_i = piQ_i (Q^-1 1)_i,  piQ_i = Q[0, i]
+ * (built on the host by pht_loglik_build; Q^-1 s and Q^-1 1 are solved
+ * against Q, so that sum_i a_i = s_1 and sum_i b_i = 1 hold to rounding).
+ * The sum is taken with the largest eigenvalue factored out,
+ *   l = lmax y + log sum_i c_i exp((lambda_i - lmax) y),
+ * so the far tail stays finite (the unshifted sum underflows to log 0).
+ *
+ * Only real, diagonalisable spectra are evaluated.  A draw whose dgeevx
+ * fails, whose spectrum has a non-zero imaginary part or whose coefficients
+ * are not finite carries a non-zero flag word and is never evaluated: its
+ * log-likelihood is reported as NaN.
+ *
+ * Every operation is explicit (fma where written, nothing else contracted:
+ * every translation unit that includes this is compiled with
+ * -ffp-contract=off), exp and log are include/pht_detmath.h's, so a GPU lane
+ * and the CPU restatement give the same bits.
+ */
+#ifndef PHT_LOGLIK_H
+#define PHT_LOGLIK_H
+
+#include "pht_detmath.h"
+
+/* ---- per-draw block: 64-bit words [flag][lmax][dl n][a n][b n] ---------- */
+#define PHT_LL_FLAG 0
+#define PHT_LL_LMAX 1
+#define PHT_LL_DL 2
+PHT_HD int pht_ll_words(int n) { return 2 + 3 * n; }
+PHT_HD int pht_ll_off_a(int n) { return PHT_LL_DL + n; }
+PHT_HD int pht_ll_off_b(int n) { return PHT_LL_DL + 2 * n; }
+
+/* flag word (0 = usable) */
+#define PHT_LL_F_INFO 1u      /* dgeevx / dgetrf / dgetri reported info != 0 */
+#define PHT_LL_F_COMPLEX 2u   /* an eigenvalue with a non-zero imaginary part */
+#define PHT_LL_F_NONFINITE 4u /* a non-finite eigenvalue or coefficient */
+
+/* totals per draw: int64 words [H, F, nbad, nobs] */
+#define PHT_LL_TOT 4
+/* an observation with |l| >= 2^40 counts as bad */
+#define PHT_LL_HMAX 1099511627776.0
+#define PHT_LL_FSCALE 4294967296.0 /* 2^32 */
+
+/* one term of the shifted sum: acc + c exp(dl y) */
+PHT_HD double pht_ll_expterm(double dl, double y) { return pht_exp(dl * y); }
+
+/* l from the finished sum; *bad = 1 when the observation is bad for this
+ * draw (acc <= 0, acc or l not finite, |l| >= 2^40), and the value is NaN */
+PHT_HD double pht_ll_finish(double lmax, double y, double acc, int *bad) {
+  const int ok_acc = (acc > 0.0) && (acc < INFINITY);
+  const double l = fma(lmax, y, pht_log(ok_acc ? acc : 1.0));
+  const int ok = ok_acc && (fabs(l) < PHT_LL_HMAX);
+  *bad = !ok;
+  return ok ? l : NAN;
+}
+
+/* l(y | draw) for one observation from one block (n <= 32) */
+PHT_HD double pht_ll_eval(int n, const double *blk, double y, int cens, int *bad) {
+  const double *dl = blk + PHT_LL_DL;
+  const double *c = blk + (cens ? pht_ll_off_b(n) : pht_ll_off_a(n));
+  double acc = 0.0;
+  for (int i = 0; i < n; i++) acc = fma(c[i], pht_ll_expterm(dl[i], y), acc);
+  return pht_ll_finish(blk[PHT_LL_LMAX], y, acc, bad);
+}
+
+/* fixed-point words of a finite l, |l| < 2^40: l = h + f 2^-32 up to 2^-33 */
+PHT_HD void pht_ll_fixed(double l, long long *h, long long *f) {
+  const double hd = rint(l);
+  *h = (long long)hd;
+  *f = llrint((l - hd) * PHT_LL_FSCALE);
+}
+
+/* ---- WAIC accumulators: six words per observation ------------------------ */
+/* all zero = no finite draw yet.  ref: the first finite l (the sums S1, S2
+ * are of u = l - ref); m, r: running max and sum_d exp(l_d - m). */
+typedef struct {
+  double ref, S1, S2, m, r;
+  long long cnt;
+} pht_waic_t;
+
+/* one finite l, in draw-index order */
+PHT_HD void pht_waic_update(pht_waic_t *w, double l) {
+  if (w->cnt == 0) {
+    w->ref = l;
+    w->m = l;
+    w->r = 1.0;
+    w->S1 = 0.0;
+    w->S2 = 0.0;
+    w->cnt = 1;
+    return;
+  }
+  const double u = l - w->ref;
+  w->S1 = w->S1 + u;
+  w->S2 = fma(u, u, w->S2);
+  w->cnt += 1;
+  const int up = l > w->m;
+  const double e = pht_exp(up ? w->m - l : l - w->m);
+  w->r = up ? fma(w->r, e, 1.0) : w->r + e;
+  w->m = up ? l : w->m;
+}
+
+#endif /* PHT_LOGLIK_H */

@@ -24,7 +24,8 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains", "PhaseTypeError", "METHODS"]
+__all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains", "PhaseTypeError", "METHODS",
+           "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -51,6 +52,8 @@ EXPORTS = [
     "pht_ctx_sweep_debug", "pht_ctx_last_kernel_ms", "pht_ctx_flagged_obs", "pht_ctx_set_global_count", "pht_gibbs_run",
     "pht_gibbs_run_resident",
     "pht_gibbs_run_chains", "pht_rccl_unique_id", "pht_ctx_rccl_prepare", "pht_ctx_attach_rccl", "pht_ctx_rccl_allreduce",
+    "pht_loglik_bytes", "pht_loglik_build", "pht_theta_to_S", "pht_ctx_loglik", "pht_ctx_loglik_reset",
+    "pht_ctx_loglik_state",
 ]
 
 
@@ -130,6 +133,12 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_attach_rccl.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
     L.pht_ctx_rccl_allreduce.argtypes = [C.c_void_p, _lp, C.c_int]
     L.LJMA_Gibbs.argtypes = [_ip, _ip, _ip, _ip, _ip, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _ip, _dp]
+    L.pht_loglik_bytes.argtypes = [C.c_int]
+    L.pht_loglik_build.argtypes = [C.c_int, _dp, _dp, C.c_void_p, C.c_int]
+    L.pht_theta_to_S.argtypes = [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp]
+    L.pht_ctx_loglik.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _lp, C.c_void_p, C.c_int]
+    L.pht_ctx_loglik_reset.argtypes = [C.c_void_p]
+    L.pht_ctx_loglik_state.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -308,6 +317,63 @@ class Sweeper:
         self.flagged_obs = int(self.L.pht_ctx_flagged_obs(self.ctx))
         return res.reshape(m, it).T.copy()
 
+    def loglik_blocks(self, blocks, batch: int = 64, pointwise: bool = False, accumulate: bool = False):
+        """pht_ctx_loglik on per-draw blocks (``loglik_block``; uint8
+        [draws, pht_loglik_bytes(n)]) over this shard's observations.
+
+        Returns ``H, F, nbad, nobs`` (int64 per draw), ``bad_draw`` (the
+        draw's flag word is non-zero: complex or defective spectrum, never
+        evaluated), ``total`` (``loglik_total`` of this shard's words) and,
+        with ``pointwise``, l[draw, observation] in the caller's order.
+        ``accumulate`` feeds the per-observation WAIC state (waic_state).
+
+        The words are exact integer sums, so shards and ranks add::
+
+            w = np.stack([r["H"], r["F"], r["nbad"], r["nobs"]])
+            reduce(w)                      # the int64 sum gibbs() is given
+            total = loglik_total(w[0], w[1], w[2], r["bad_draw"])
+        """
+        blocks = np.ascontiguousarray(blocks, np.uint8)
+        nb = self.L.pht_loglik_bytes(self.n)
+        if blocks.ndim != 2 or blocks.shape[1] != nb:
+            raise ValueError(f"blocks must be [draws, {nb}] bytes for n = {self.n}")
+        nd = blocks.shape[0]
+        tot = np.zeros(4 * nd, np.int64)
+        pw = np.full((nd, self.count), np.nan) if pointwise else None
+        if self.L.pht_ctx_loglik(self.ctx, nd, blocks.ctypes.data, int(batch), tot,
+                                 pw.ctypes.data if pointwise else None, int(bool(accumulate))) != 0:
+            raise _err(self.L)
+        tot = tot.reshape(nd, 4)
+        bad_draw = blocks[:, :8].copy().view(np.uint64).reshape(nd) != 0
+        out = dict(H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(),
+                   bad_draw=bad_draw)
+        out["total"] = loglik_total(out["H"], out["F"], out["nbad"], bad_draw)
+        if pointwise:
+            out["pointwise"] = pw
+        return out
+
+    def loglik(self, S_list, s_list, batch: int = 64, pointwise: bool = False, accumulate: bool = False):
+        """Observed-data log-likelihood of each draw (S, s) over this shard:
+        sum of log f(y) over exact and log Fbar(y) over censored observations
+        (include/pht_loglik.h); see loglik_blocks for the result."""
+        blocks = np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)])
+        return self.loglik_blocks(blocks, batch=batch, pointwise=pointwise, accumulate=accumulate)
+
+    def waic_reset(self) -> None:
+        """Forget the per-observation WAIC state (pht_ctx_loglik_reset)."""
+        if self.L.pht_ctx_loglik_reset(self.ctx) != 0:
+            raise _err(self.L)
+
+    def waic_state(self):
+        """The per-observation WAIC accumulators (pht_waic_t), in the caller's
+        observation order: dict(ref, S1, S2, m, r, cnt)."""
+        d = {k: np.zeros(self.count, np.float64) for k in ("ref", "S1", "S2", "m", "r")}
+        cnt = np.zeros(self.count, np.int32)
+        if self.L.pht_ctx_loglik_state(self.ctx, d["ref"], d["S1"], d["S2"], d["m"], d["r"], cnt) != 0:
+            raise _err(self.L)
+        d["cnt"] = cnt
+        return d
+
     def close(self):
         if self.ctx:
             self.L.pht_ctx_destroy(self.ctx)
@@ -475,3 +541,158 @@ def phtMCMC(x, states, beta, nu, zeta, n, mhit=1, resume=None, silent=False, col
     zeta_d = dict(zip(names, zrep[:len(names)]))
     return phtMCMC2(x, TT, beta, nu_d, zeta_d, n, censored=None, C_=np.ones((states + 1, states + 1)),
                     method="MHRS", mhit=mhit, resume=resume, silent=silent, collation=collation)
+
+
+# ------------------------------------------------- log-likelihood of the draws
+# No reference counterpart: the reference returns the draws only.  The
+# arithmetic is specified in include/pht_loglik.h and runs in
+# phasetype_amd/csrc/pht_loglik.hip; spectral evaluation only (a draw with a
+# complex or defective spectrum is reported as NaN and never evaluated).
+def loglik_block(S, s) -> np.ndarray:
+    """One draw's block for ``Sweeper.loglik_blocks`` (pht_loglik_build; host
+    only): uint8[pht_loglik_bytes(n)].  An unusable draw (complex or defective
+    spectrum, non-finite entry) has a non-zero first word."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    nb = L.pht_loglik_bytes(n)
+    if nb < 0 or S.shape != (n, n):
+        raise ValueError(f"S must be square with 1 <= n <= 32, got {S.shape}")
+    out = np.zeros(nb, np.uint8)
+    Sf = np.ascontiguousarray(S.reshape(-1, order="F"))
+    if L.pht_loglik_build(n, Sf, np.ascontiguousarray(s, np.float64), out.ctypes.data, nb) < 0:
+        raise _err(L)
+    return out
+
+
+def loglik_total(H, F, nbad, bad_draw) -> np.ndarray:
+    """The log-likelihood per draw from its (summed) fixed-point words:
+    H + F 2^-32; -inf where an observation was bad; NaN for an unusable draw."""
+    H, F = np.asarray(H, np.int64), np.asarray(F, np.int64)
+    tot = H.astype(np.float64) + F.astype(np.float64) * 2.0 ** -32
+    tot = np.where(np.asarray(nbad) > 0, -np.inf, tot)
+    return np.where(np.asarray(bad_draw, bool), np.nan, tot)
+
+
+def _tt_numbers(TT_or_T, collation: str = "C"):
+    """(T as int32 [n+1, n+1], variable names or None): a matrix of names is
+    numbered as phtMCMC2 does (sorted names without "0" -> 1..m, which is the
+    column order of its samples); a matrix of integers is taken as T."""
+    A = np.asarray(TT_or_T)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 2:
+        raise ValueError("matrix of variables must be square")
+    if A.dtype.kind in "iu":
+        return np.ascontiguousarray(A, np.int32), None
+    TT = np.asarray(TT_or_T, dtype=object).astype(str)
+    var_names = [v for v in _r_sort(set(TT.reshape(-1)), collation) if v != "0"]
+    TN = np.zeros(TT.shape, np.int32)
+    for i in range(TT.shape[0]):
+        for j in range(TT.shape[1]):
+            TN[i, j] = (["0"] + var_names).index(TT[i, j])
+    return TN, var_names
+
+
+def theta_to_S(theta, T, C_=None):
+    """One row of a chain -> (S [n, n], s [n]) (pht_theta_to_S: the T / C maps
+    of the Gibbs loop; T numbers as ``_tt_numbers`` gives them)."""
+    L = load()
+    T = np.asarray(T, np.int32)
+    n1 = T.shape[0]
+    n = n1 - 1
+    C_ = np.ones((n1, n1)) if C_ is None else np.asarray(C_, np.float64)
+    theta = np.ascontiguousarray(theta, np.float64)
+    S, s = np.zeros(n * n), np.zeros(n)
+    Tf = np.ascontiguousarray(T.reshape(-1, order="F"), np.int32)
+    Cf = np.ascontiguousarray(C_.reshape(-1, order="F"), np.float64)
+    if L.pht_theta_to_S(n, len(theta), Tf, Cf, theta, S, s) != 0:
+        raise _err(L)
+    return S.reshape(n, n, order="F"), s
+
+
+def _chain_blocks(res, TT_or_T, C_, n, collation="C"):
+    """(blocks uint8 [draws, bytes], n) for the rows of a chain: ``res`` is the
+    dict phtMCMC2 / phtMCMC return or the it x m array of Sweeper.gibbs."""
+    if isinstance(res, dict):
+        samples = np.asarray(res["samples"], np.float64)
+        if TT_or_T is None:
+            TT_or_T = res["TT"]
+    else:
+        samples = np.asarray(res, np.float64)
+    samples = np.atleast_2d(samples)
+    T, names = _tt_numbers(TT_or_T, collation)
+    if n is not None and int(n) != T.shape[0] - 1:
+        raise ValueError(f"n = {n} does not match the {T.shape[0]} x {T.shape[0]} generator")
+    if isinstance(res, dict) and names is not None and list(res.get("vars", names)) != names:
+        raise ValueError("the variables of the chain do not match the variables in the generator")
+    if samples.shape[1] != int(T.max()):
+        raise ValueError(f"the chain has {samples.shape[1]} columns, the generator {int(T.max())} variables")
+    blocks = np.stack([loglik_block(*theta_to_S(row, T, C_)) for row in samples])
+    return blocks, T.shape[0] - 1
+
+
+def _obs_sweeper(x, censored, n, device):
+    sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    sw.set_obs(np.asarray(x, np.float64), censored)
+    return sw
+
+
+def log_lik(res, x, TT_or_T=None, censored=None, C_=None, n=None, device: int = 0, batch: int = 64,
+            collation: str = "C") -> np.ndarray:
+    """The observed-data log-likelihood trace of a chain: one value per row of
+    ``res`` (the dict phtMCMC2 / phtMCMC return, or the array of
+    Sweeper.gibbs), over data ``x`` / ``censored``.  ``TT_or_T``: the matrix of
+    variable names given to phtMCMC2 (numbered as it numbers them; default the
+    chain's own) or the integer matrix T of Sweeper.gibbs.  NaN for a draw with
+    a complex or defective spectrum, -inf where an observation has no density."""
+    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        return sw.loglik_blocks(blocks, batch=batch)["total"]
+    finally:
+        sw.close()
+
+
+def waic_from_state(st) -> dict:
+    """WAIC from the per-observation accumulators (Sweeper.waic_state):
+    lppd_i = m + log r - log cnt, p_waic_i = (S2 - S1^2 / cnt) / (cnt - 1)."""
+    cnt = np.asarray(st["cnt"], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lppd_i = st["m"] + np.log(st["r"]) - np.log(cnt)
+        p_i = (st["S2"] - st["S1"] ** 2 / cnt) / (cnt - 1.0)
+    lppd, p = float(np.sum(lppd_i)), float(np.sum(p_i))
+    return dict(elpd_waic=lppd - p, p_waic=p, lppd=lppd, waic=-2.0 * (lppd - p), pointwise=(lppd_i, p_i),
+                n_draws_used=int(np.max(st["cnt"])) if len(cnt) else 0)
+
+
+def waic(res, x, TT_or_T=None, censored=None, C_=None, n=None, burn: int = 0, device: int = 0, batch: int = 64,
+         collation: str = "C") -> dict:
+    """WAIC of a chain (rows from ``burn`` on) over data ``x`` / ``censored``:
+    dict(elpd_waic, p_waic, lppd, waic, pointwise=(lppd_i, p_waic_i),
+    n_draws_used).  Draws with a complex or defective spectrum are left out."""
+    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        sw.waic_reset()
+        r = sw.loglik_blocks(blocks[int(burn):], batch=batch, accumulate=True)
+        out = waic_from_state(sw.waic_state())
+        out["n_draws_used"] = int(np.sum(~r["bad_draw"]))
+        return out
+    finally:
+        sw.close()
+
+
+def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int = 64, collation: str = "C") -> dict:
+    """Per-draw curves on ``grid``: dict(logdens, logsurv, hazard), each
+    [draws, len(grid)] (the grid as exact, then as censored observations, in
+    pointwise mode).  Bands: ``np.quantile(out["hazard"], [.025, .975], axis=0)``."""
+    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    grid = np.ascontiguousarray(grid, np.float64)
+    sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    try:
+        sw.set_obs(grid, np.zeros(len(grid), np.int32))
+        ld = sw.loglik_blocks(blocks, batch=batch, pointwise=True)["pointwise"]
+        sw.set_obs(grid, np.ones(len(grid), np.int32))
+        ls = sw.loglik_blocks(blocks, batch=batch, pointwise=True)["pointwise"]
+    finally:
+        sw.close()
+    return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))

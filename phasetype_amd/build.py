@@ -2,7 +2,8 @@
 
 hipcc for gfx950: the HIP kernels (pht_kernels_nt.hip once per compile-time
 n, in parallel, + the pht_dispatch.hip launcher), the host runtime / C ABI
-(gibbs_host.cpp) and the R-compatible stream (rstream.c), then one link.
+(gibbs_host.cpp), the R-compatible stream (rstream.c) and the log-likelihood
+kernel (pht_loglik.hip), then one link.
 ``-ffp-contract=off`` is required: the device path must reproduce the
 oracle's arithmetic bit for bit (no implicit FMA contraction anywhere).
 """
@@ -37,10 +38,13 @@ UNIT_DEFINES = {5: ("PHT_PHILOX_UNROLL",), 20: ("PHT_PHILOX_UNROLL",),
 # (source, extra defines, extra device-compile flags) per object
 UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT_FLAGS.get(k, ()))
          for k in KERNEL_NTS] + [
-    ("pht_dispatch.hip", (), ()), ("pht_resident.hip", (), ()), ("gibbs_host.cpp", (), ()), ("rstream.c", (), ())]
+    ("pht_dispatch.hip", (), ()), ("pht_resident.hip", (), ()), ("gibbs_host.cpp", (), ()), ("rstream.c", (), ()),
+    # the log-likelihood kernel (include/pht_loglik.h), a unit of its own: the sweep units compile as before
+    ("pht_loglik.hip", (), ())]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
-           "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h"]
+           "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
+           "pht_loglik_args.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
 
@@ -57,7 +61,7 @@ def inputs() -> list:
     script with its flags)."""
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
     deps += [os.path.join(REPO, "include", f) for f in ("phasetype_amd.h", "pht_detmath.h", "pht_philox.h",
-                                                          "pht_gamma.h", "pht_eigen.h")]
+                                                          "pht_gamma.h", "pht_eigen.h", "pht_loglik.h")]
     deps.append(os.path.abspath(__file__))
     return deps
 

@@ -43,6 +43,8 @@
 #include "pht_detmath.h"
 #include "pht_kernels.h"
 #include "pht_layout.h"
+#include "pht_loglik.h"
+#include "pht_loglik_args.h"
 #include "rstream.h"
 
 using namespace pht;
@@ -241,7 +243,9 @@ struct EigenWork {
   std::vector<int> iwork, ipiv;
 };
 
-static int eigen(int n, const double *S, double *evals, double *Q, double *Qinv) {
+/* evi_out: the eigenvalues' imaginary parts (the log-likelihood refuses a
+ * complex spectrum, pht_loglik_build; the sampler goes on as the reference does) */
+static int eigen(int n, const double *S, double *evals, double *Q, double *Qinv, double *evi_out = nullptr) {
   OneBlasThread one;
   char balanc = 'B', jobv = 'V', sense = 'B';
   int lwork = -1, info = 0, ilo, ihi, nn = n;
@@ -287,6 +291,7 @@ static int eigen(int n, const double *S, double *evals, double *Q, double *Qinv)
   }
   for (int i = 0; i < n; i++)
     if (evi[i] > 0) say("Error: imaginary part of eigenvalue %d found.\n", i + 1);
+  if (evi_out) memcpy(evi_out, evi, sizeof(double) * n);
   memcpy(Qinv, Q, sizeof(double) * n * n);
   p_dgetrf(&nn, &nn, Qinv, &nn, ew.ipiv.data(), &info);
   if (info != 0) {
@@ -510,6 +515,17 @@ struct pht_ctx {
   unsigned *h_gate = nullptr, *d_gate = nullptr;
   unsigned long long *h_pg = nullptr, *d_pg = nullptr;
   unsigned gate_seq = 0;
+  /* pht_ctx_loglik (allocated on first use): draw blocks and totals of a
+   * call, the pointwise staging buffer, and the WAIC state per observation in
+   * the device (sorted) order: 5 double arrays [ref S1 S2 m r] and the counts */
+  double *d_llblk = nullptr;
+  unsigned long long *d_lltot = nullptr;
+  long llblk_cap = 0, lltot_cap = 0;
+  double *d_llpw = nullptr;
+  size_t llpw_cap = 0;
+  double *d_waic = nullptr;
+  long long *d_wcnt = nullptr;
+  int ll_grid_cap = 0;
 };
 
 /* lanes of the persistent ECS grid on an MI355X (256 CUs x 2 blocks x 256) */
@@ -729,6 +745,14 @@ static void ctx_free_obs(pht_ctx *c) {
   c->utab_cap = 0;
   if (c->d_dcsb) (void)hipFree(c->d_dcsb);
   c->d_dcsb = nullptr;
+  /* per-observation log-likelihood buffers (the WAIC state is of these observations) */
+  if (c->d_llpw) (void)hipFree(c->d_llpw);
+  if (c->d_waic) (void)hipFree(c->d_waic);
+  if (c->d_wcnt) (void)hipFree(c->d_wcnt);
+  c->d_llpw = nullptr;
+  c->llpw_cap = 0;
+  c->d_waic = nullptr;
+  c->d_wcnt = nullptr;
   c->d_y = nullptr; c->d_cens = nullptr; c->d_gid = nullptr;
   c->d_mbest = c->d_mq0 = c->d_mq1 = nullptr;
   c->d_mcnt = nullptr;
@@ -1029,6 +1053,8 @@ extern "C" void pht_ctx_destroy(pht_ctx *c) {
   if (c->ev1b) (void)hipEventDestroy(c->ev1b);
   if (c->comm) rccl_destroy(c->comm);
   if (c->d_rccl) (void)hipFree(c->d_rccl);
+  if (c->d_llblk) (void)hipFree(c->d_llblk);
+  if (c->d_lltot) (void)hipFree(c->d_lltot);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -1538,20 +1564,45 @@ struct Ent {
   double c;
 };
 
+/* The map draw -> generator shared by GibbsState and pht_theta_to_S
+ * (src/PHT_MCMC_Aslett.c:214-262, :380-397): cell (i, j) of the (n+1)^2
+ * matrix TT with T[i + j n1] = k + 1 holds theta_k C[i + j n1]; the diagonal
+ * of a transient row is minus the sum of the row's cells. */
+inline double tt_cell(double theta, double c) { return theta * c; }
+/* row i's diagonal.  reverse = false: cells by increasing column (how the
+ * reference initialises the chain); true: by decreasing column, the
+ * reverse-insertion order in which its update refreshes every later draw */
+inline double tt_diag(int n1, const int *T, const double *TT, int i, bool reverse) {
+  double tmp = 0.0;
+  for (int q = 0; q < n1; q++) {
+    const int j = reverse ? n1 - 1 - q : q;
+    if (T[i + j * n1] != 0) tmp -= TT[i + j * n1];
+  }
+  return tmp;
+}
+/* (S, s) = the transient block and exit column of TT */
+inline void tt_split(int n, const double *TT, double *S, double *s) {
+  const int n1 = n + 1;
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) S[i + j * n] = TT[i + j * n1];
+  for (int i = 0; i < n; i++) s[i] = TT[i + n * n1];
+}
+
 /* The reference's Gibbs bookkeeping (src/PHT_MCMC_Aslett.c:187-405) with
  * the linked lists kept as arrays visited in list (reverse-insertion)
  * order, so zsum and the diagonal refresh sum in the reference's order. */
 struct GibbsState {
   int it, n, m, n1;
   const double *nu, *zeta;
+  const int *T;
   double *res;
   std::vector<double> TT, S, s;
   std::vector<std::vector<Ent>> Nl, Sl, sl, zl, TTl, Dl;
 
   template <class Rng>
-  GibbsState(Rng &R, int it_, int n_, int m_, const double *nu_, const double *zeta_, const int *T, const double *C,
+  GibbsState(Rng &R, int it_, int n_, int m_, const double *nu_, const double *zeta_, const int *T_, const double *C,
              const double *start, double *res_)
-      : it(it_), n(n_), m(m_), n1(n_ + 1), nu(nu_), zeta(zeta_), res(res_) {
+      : it(it_), n(n_), m(m_), n1(n_ + 1), nu(nu_), zeta(zeta_), T(T_), res(res_) {
     TT.assign(n1 * n1, 0.0);
     S.assign(n * n, 0.0);
     s.assign(n, 0.0);
@@ -1562,7 +1613,6 @@ struct GibbsState {
     } else {
       for (int i = 0; i < m; i++) res[0 + (size_t)i * it] = start[i];
     }
-    double rsum = 0.0;
     for (int i = 0; i < n1; i++) {
       for (int j = 0; j < n1; j++) {
         const int t = T[i + j * n1];
@@ -1572,7 +1622,7 @@ struct GibbsState {
         }
         const int k = t - 1;
         const double c = C[i + j * n1];
-        rsum -= TT[i + j * n1] = res[0 + (size_t)k * it] * c;
+        TT[i + j * n1] = tt_cell(res[0 + (size_t)k * it], c);
         if (j == n) {
           Nl[k].push_back({i, i, 1.0});
           sl[k].push_back({i, 0, c});
@@ -1584,12 +1634,9 @@ struct GibbsState {
         TTl[k].push_back({i, j, c});
         Dl[i].push_back({i, j, 1.0});
       }
-      TT[i + i * n1] = rsum;
-      rsum = 0.0;
+      TT[i + i * n1] = tt_diag(n1, T, TT.data(), i, false);
     }
-    for (int i = 0; i < n; i++)
-      for (int j = 0; j < n; j++) S[i + j * n] = TT[i + j * n1];
-    for (int i = 0; i < n; i++) s[i] = TT[i + n * n1];
+    tt_split(n, TT.data(), S.data(), s.data());
   }
 
   /* steps 4-5 (:340-397): compile statistics and draw from the posteriors */
@@ -1604,13 +1651,13 @@ struct GibbsState {
     for (int k = 0; k < m; k++) {
       const double tmp = res[iter + (size_t)k * it] =
           R.gamma(nu[k] + (double)(int)Nsum[k], 1.0 / (zeta[k] + zsum[k]));
-      for (int e = (int)TTl[k].size() - 1; e >= 0; e--) TT[TTl[k][e].i + TTl[k][e].j * n1] = tmp * TTl[k][e].c;
-      for (int e = (int)Sl[k].size() - 1; e >= 0; e--) S[Sl[k][e].i + Sl[k][e].j * n] = tmp * Sl[k][e].c;
-      for (int e = (int)sl[k].size() - 1; e >= 0; e--) s[sl[k][e].i] = tmp * sl[k][e].c;
+      for (int e = (int)TTl[k].size() - 1; e >= 0; e--)
+        TT[TTl[k][e].i + TTl[k][e].j * n1] = tt_cell(tmp, TTl[k][e].c);
+      for (int e = (int)Sl[k].size() - 1; e >= 0; e--) S[Sl[k][e].i + Sl[k][e].j * n] = tt_cell(tmp, Sl[k][e].c);
+      for (int e = (int)sl[k].size() - 1; e >= 0; e--) s[sl[k][e].i] = tt_cell(tmp, sl[k][e].c);
     }
-    for (int i = 0; i < n; i++) {
-      double tmp = 0.0;
-      for (int e = (int)Dl[i].size() - 1; e >= 0; e--) tmp -= TT[Dl[i][e].i + Dl[i][e].j * n1];
+    for (int i = 0; i < n; i++) { /* Dl[i] in reverse = the row's cells by decreasing column */
+      const double tmp = tt_diag(n1, T, TT.data(), i, true);
       TT[i + i * n1] = tmp;
       S[i + i * n] = tmp;
     }
@@ -2202,6 +2249,267 @@ extern "C" int pht_gibbs_run_resident(pht_ctx *c, int it, int method, int m, con
   }
   if (fl)
     warn("\nWARNING: %llu observation-sweeps hit a sampler cap or numerical guard in the resident chain\n", fl);
+  return 0;
+}
+
+/* ============================================ log-likelihood of posterior draws */
+/*
+ * No reference counterpart: the reference returns the draws and nothing
+ * else.  Specification in include/pht_loglik.h; the kernel is
+ * pht_loglik.hip.  Spectral evaluation only: a draw whose spectrum is complex
+ * (the sampler warns and uses the real parts, as the reference does), whose
+ * LAPACK call fails or whose coefficients are not finite is flagged and never
+ * evaluated.
+ */
+/* x1 = Q^-1 r1, x2 = Q^-1 r2 by Gaussian elimination with partial pivoting
+ * (column-major Q, n <= kMaxN).  Solving against Q keeps Q x - r at rounding
+ * level, which is what the coefficients need: sum_i Q[0,i] x_i must give back
+ * r_1 (the density at 0 is s_1, the survival 1).  eigen()'s dgetri inverse,
+ * kept as the reference computes it, bounds X Q - I instead, and the
+ * coefficients from it were off by ~100 cond(Q) ulps at n = 15. */
+static bool solve_pair(int n, const double *Q, const double *r1, const double *r2, double *x1, double *x2) {
+  std::vector<double> A(Q, Q + (size_t)n * n);
+  for (int i = 0; i < n; i++) {
+    x1[i] = r1[i];
+    x2[i] = r2[i];
+  }
+  for (int k = 0; k < n; k++) {
+    int p = k;
+    for (int i = k + 1; i < n; i++)
+      if (fabs(A[i + k * n]) > fabs(A[p + k * n])) p = i;
+    if (!(fabs(A[p + k * n]) > 0.0) || !std::isfinite(A[p + k * n])) return false;
+    if (p != k) {
+      for (int j = 0; j < n; j++) std::swap(A[k + j * n], A[p + j * n]);
+      std::swap(x1[k], x1[p]);
+      std::swap(x2[k], x2[p]);
+    }
+    for (int i = k + 1; i < n; i++) {
+      const double f = A[i + k * n] / A[k + k * n];
+      for (int j = k + 1; j < n; j++) A[i + j * n] -= f * A[k + j * n];
+      x1[i] -= f * x1[k];
+      x2[i] -= f * x2[k];
+    }
+  }
+  for (int k = n - 1; k >= 0; k--) {
+    for (int j = k + 1; j < n; j++) {
+      x1[k] -= A[k + j * n] * x1[j];
+      x2[k] -= A[k + j * n] * x2[j];
+    }
+    x1[k] /= A[k + k * n];
+    x2[k] /= A[k + k * n];
+  }
+  return true;
+}
+
+extern "C" int pht_loglik_bytes(int n) { return (n < 1 || n > kMaxN) ? -1 : 8 * pht_ll_words(n); }
+
+extern "C" int pht_loglik_build(int n, const double *S, const double *s, unsigned char *out, int out_bytes) {
+  if (n < 1 || n > kMaxN) {
+    set_err("pht_loglik_build: n = %d outside 1..%d", n, kMaxN);
+    return -1;
+  }
+  const int words = pht_ll_words(n);
+  if (!S || !s || !out || out_bytes < 8 * words) {
+    set_err("pht_loglik_build: null argument or out_bytes < %d", 8 * words);
+    return -2;
+  }
+  if (!lapack_ready()) {
+    set_err("no LAPACK bound (call pht_bind_lapack or set PHT_LAPACK_LIB)");
+    return -1;
+  }
+  std::vector<double> w(words, 0.0), ev(n, 0.0), evi(n, 0.0), Q(n * n, 0.0), Qinv(n * n, 0.0), Qs(n, 0.0), Q1(n, 0.0);
+  uint64_t flag = 0;
+  bool finite = true;
+  for (int k = 0; k < n * n; k++) finite = finite && std::isfinite(S[k]);
+  for (int k = 0; k < n; k++) finite = finite && std::isfinite(s[k]);
+  if (!finite) {
+    flag |= PHT_LL_F_NONFINITE; /* (LAPACK is not asked about such a matrix) */
+  } else if (eigen(n, S, ev.data(), Q.data(), Qinv.data(), evi.data()) != 0) {
+    flag |= PHT_LL_F_INFO;
+  } else {
+    for (int i = 0; i < n; i++)
+      if (evi[i] != 0.0) flag |= PHT_LL_F_COMPLEX;
+    const std::vector<double> ones(n, 1.0);
+    if (!solve_pair(n, Q.data(), s, ones.data(), Qs.data(), Q1.data())) flag |= PHT_LL_F_INFO;
+    double lmax = ev[0];
+    for (int i = 1; i < n; i++)
+      if (ev[i] > lmax) lmax = ev[i];
+    w[PHT_LL_LMAX] = lmax;
+    for (int i = 0; i < n; i++) {
+      const double piQ = Q[0 + i * n]; /* pi = e_1 */
+      const double dl = ev[i] - lmax, a = piQ * Qs[i], b = piQ * Q1[i];
+      if (!std::isfinite(ev[i]) || !std::isfinite(a) || !std::isfinite(b)) flag |= PHT_LL_F_NONFINITE;
+      w[PHT_LL_DL + i] = dl;
+      w[pht_ll_off_a(n) + i] = a;
+      w[pht_ll_off_b(n) + i] = b;
+    }
+  }
+  if (flag) std::fill(w.begin(), w.end(), 0.0);
+  memcpy(out, w.data(), 8 * (size_t)words);
+  memcpy(out + 8 * PHT_LL_FLAG, &flag, 8);
+  return (int)flag;
+}
+
+extern "C" int pht_theta_to_S(int n, int m, const int *T, const double *C, const double *theta, double *S,
+                              double *s) {
+  if (n < 1 || n > kMaxN || m < 1 || !T || !C || !theta || !S || !s) {
+    set_err("pht_theta_to_S: invalid argument");
+    return -1;
+  }
+  const int n1 = n + 1;
+  std::vector<double> TT((size_t)n1 * n1, 0.0);
+  for (int i = 0; i < n1; i++)
+    for (int j = 0; j < n1; j++) {
+      const int t = T[i + j * n1];
+      if (t == 0) continue;
+      if (t < 1 || t > m) {
+        set_err("pht_theta_to_S: T[%d,%d] = %d outside 0..m", i, j, t);
+        return -1;
+      }
+      TT[i + j * n1] = tt_cell(theta[t - 1], C[i + j * n1]);
+    }
+  /* the diagonal as GibbsState::update leaves it for every drawn row */
+  for (int i = 0; i < n; i++) TT[i + i * n1] = tt_diag(n1, T, TT.data(), i, true);
+  tt_split(n, TT.data(), S, s);
+  return 0;
+}
+
+static int loglik_waic_alloc(pht_ctx *c) {
+  if (c->d_waic) return 0;
+  HIPCHK(hipMalloc(&c->d_waic, sizeof(double) * 5 * (size_t)c->count));
+  HIPCHK(hipMalloc(&c->d_wcnt, sizeof(long long) * (size_t)c->count));
+  HIPCHK(hipMemsetAsync(c->d_waic, 0, sizeof(double) * 5 * (size_t)c->count, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_wcnt, 0, sizeof(long long) * (size_t)c->count, c->stream));
+  return 0;
+}
+
+static int loglik_need_obs(pht_ctx *c, const char *who) {
+  if (!c) {
+    set_err("%s: null context", who);
+    return -1;
+  }
+  if (c->count < 1 || !c->d_y) {
+    set_err("%s: no observations set on this context (pht_ctx_set_obs)", who);
+    return -1;
+  }
+  return 0;
+}
+
+extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
+                              double *pointwise, int accumulate) {
+  if (loglik_need_obs(c, "pht_ctx_loglik")) return -1;
+  if (ndraws < 1 || !blocks || !totals || batch < 1 || batch > kLoglikBatch) {
+    set_err("pht_ctx_loglik: need ndraws >= 1, blocks, totals and 1 <= batch <= %d", kLoglikBatch);
+    return -1;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  ctx_drain(c);
+  const int n = c->n, words = pht_ll_words(n);
+  const long count = c->count;
+  if (!c->ll_grid_cap) {
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->ll_grid_cap = std::max(1, cus) * 4;
+  }
+  if (c->llblk_cap < (long)ndraws * words) {
+    if (c->d_llblk) (void)hipFree(c->d_llblk);
+    c->d_llblk = nullptr;
+    c->llblk_cap = 0;
+    HIPCHK(hipMalloc(&c->d_llblk, sizeof(double) * (size_t)ndraws * words));
+    c->llblk_cap = (long)ndraws * words;
+  }
+  if (c->lltot_cap < (long)ndraws * PHT_LL_TOT) {
+    if (c->d_lltot) (void)hipFree(c->d_lltot);
+    c->d_lltot = nullptr;
+    c->lltot_cap = 0;
+    HIPCHK(hipMalloc(&c->d_lltot, sizeof(unsigned long long) * (size_t)ndraws * PHT_LL_TOT));
+    c->lltot_cap = (long)ndraws * PHT_LL_TOT;
+  }
+  const int bmax = std::min(batch, ndraws);
+  if (pointwise && c->llpw_cap < (size_t)bmax * (size_t)count) {
+    if (c->d_llpw) (void)hipFree(c->d_llpw);
+    c->d_llpw = nullptr;
+    c->llpw_cap = 0;
+    HIPCHK(hipMalloc(&c->d_llpw, sizeof(double) * (size_t)bmax * (size_t)count));
+    c->llpw_cap = (size_t)bmax * (size_t)count;
+  }
+  if (accumulate && loglik_waic_alloc(c)) return -1;
+  HIPCHK(hipMemcpyAsync(c->d_llblk, blocks, 8 * (size_t)ndraws * words, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_lltot, 0, sizeof(unsigned long long) * (size_t)ndraws * PHT_LL_TOT, c->stream));
+  std::vector<double> hpw;
+  if (pointwise) hpw.resize((size_t)bmax * (size_t)count);
+  /* device time of the call's launches (pointwise mode: with the copies
+   * between them), read through pht_ctx_last_kernel_ms */
+  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  for (int d0 = 0; d0 < ndraws; d0 += batch) {
+    const int nb = std::min(batch, ndraws - d0);
+    LoglikArgs a{};
+    a.n = n;
+    a.nd = nb;
+    a.count = count;
+    a.y = c->d_y;
+    a.cens = c->d_cens;
+    a.blocks = c->d_llblk + (size_t)d0 * words;
+    a.totals = c->d_lltot + (size_t)d0 * PHT_LL_TOT;
+    a.pw = pointwise ? c->d_llpw : nullptr;
+    a.acc = accumulate ? 1 : 0;
+    if (accumulate) {
+      a.w_ref = c->d_waic;
+      a.w_S1 = c->d_waic + count;
+      a.w_S2 = c->d_waic + 2 * count;
+      a.w_m = c->d_waic + 3 * count;
+      a.w_r = c->d_waic + 4 * count;
+      a.w_cnt = c->d_wcnt;
+    }
+    HIPCHK(pht_launch_loglik(&a, c->ll_grid_cap, c->stream));
+    if (pointwise) {
+      HIPCHK(hipMemcpyAsync(hpw.data(), c->d_llpw, sizeof(double) * (size_t)nb * (size_t)count,
+                            hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      for (int d = 0; d < nb; d++) { /* back to the caller's observation order */
+        const double *src = hpw.data() + (size_t)d * count;
+        double *dst = pointwise + (size_t)(d0 + d) * count;
+        for (long k = 0; k < count; k++) dst[c->order[k]] = src[k];
+      }
+    }
+  }
+  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(hipMemcpyAsync(totals, c->d_lltot, sizeof(long long) * (size_t)ndraws * PHT_LL_TOT, hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+  return 0;
+}
+
+extern "C" int pht_ctx_loglik_reset(pht_ctx *c) {
+  if (loglik_need_obs(c, "pht_ctx_loglik_reset")) return -1;
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->d_waic) return loglik_waic_alloc(c);
+  HIPCHK(hipMemsetAsync(c->d_waic, 0, sizeof(double) * 5 * (size_t)c->count, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_wcnt, 0, sizeof(long long) * (size_t)c->count, c->stream));
+  return 0;
+}
+
+extern "C" int pht_ctx_loglik_state(pht_ctx *c, double *ref, double *S1, double *S2, double *m, double *r, int *cnt) {
+  if (loglik_need_obs(c, "pht_ctx_loglik_state")) return -1;
+  if (!ref || !S1 || !S2 || !m || !r || !cnt) {
+    set_err("pht_ctx_loglik_state: null output");
+    return -1;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (loglik_waic_alloc(c)) return -1;
+  const long count = c->count;
+  std::vector<double> h(5 * (size_t)count);
+  std::vector<long long> hc(count);
+  HIPCHK(hipMemcpyAsync(h.data(), c->d_waic, sizeof(double) * 5 * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hc.data(), c->d_wcnt, sizeof(long long) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  double *outs[5] = {ref, S1, S2, m, r};
+  for (long k = 0; k < count; k++) {
+    const long o = c->order[k];
+    for (int q = 0; q < 5; q++) outs[q][o] = h[(size_t)q * count + k];
+    cnt[o] = (int)hc[k];
+  }
   return 0;
 }
 
