@@ -1,7 +1,7 @@
 /*
  * pht_loglik.h — specification of the observed-data log-likelihood of a
  * posterior draw, shared by the HIP kernel (phasetype_amd/csrc/pht_loglik.hip),
- * the host (gibbs_host.cpp) and the tests' CPU restatement
+ * the host (host_loglik.cpp) and the tests' CPU restatement
  * (tests/loglik_spec.c).
  *
  * For a draw theta -> (S, s) with S = Q diag(lambda) Q^-1 and pi = e_1 (as in

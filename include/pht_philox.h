@@ -6,7 +6,7 @@
  * replay.  The device path therefore draws every uniform from
  * Philox4x32-10 (Salmon et al., SC'11; Random123 constants), addressed by
  *   key     = (k0, k1)                  — two words from R's stream at
- *                                         LJMA_Gibbs entry (gibbs_host.cpp)
+ *                                         LJMA_Gibbs entry (host_r.cpp)
  *   counter = (obs, stream, sweep, blk) — obs index, stream tag (0 = main),
  *                                         Gibbs sweep, block index
  * An observation's stream is the word sequence block 0 words 0..3, block 1

@@ -2,8 +2,8 @@
 
 hipcc for gfx950: the HIP kernels (pht_kernels_nt.hip once per compile-time
 n, in parallel, + the pht_dispatch.hip launcher), the host runtime / C ABI
-(gibbs_host.cpp), the R-compatible stream (rstream.c) and the log-likelihood
-kernel (pht_loglik.hip), then one link.
+(the host_*.cpp units, csrc/host_internal.h), the R-compatible stream
+(rstream.c) and the log-likelihood kernel (pht_loglik.hip), then one link.
 ``-ffp-contract=off`` is required: the device path must reproduce the
 oracle's arithmetic bit for bit (no implicit FMA contraction anywhere).
 """
@@ -35,16 +35,20 @@ UNIT_FLAGS = {10: ("-mllvm", "--amdgpu-schedule-metric-bias=0")}
 # -0.9 %; the censored kernel's: neutral) (profiles/r06/unroll/)
 UNIT_DEFINES = {5: ("PHT_PHILOX_UNROLL",), 20: ("PHT_PHILOX_UNROLL",),
                 10: ("PHT_ECS_PHILOX_UNROLL",), 15: ("PHT_MHRS_PHILOX_UNROLL", "PHT_ECS_PHILOX_UNROLL")}
-# (source, extra defines, extra device-compile flags) per object
+# the host runtime, one job per unit (csrc/host_internal.h lists them)
+HOST_UNITS = ("host_r.cpp", "host_params.cpp", "host_ctx.cpp", "host_chains.cpp", "host_rccl.cpp", "host_gibbs.cpp",
+              "host_resident.cpp", "host_loglik.cpp")
+# (source, extra defines, extra device-compile flags) per object; the kernel
+# units first: the long compiles start first
 UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT_FLAGS.get(k, ()))
          for k in KERNEL_NTS] + [
-    ("pht_dispatch.hip", (), ()), ("pht_resident.hip", (), ()), ("gibbs_host.cpp", (), ()), ("rstream.c", (), ()),
+    ("pht_dispatch.hip", (), ()), ("pht_resident.hip", (), ()),
     # the log-likelihood kernel (include/pht_loglik.h), a unit of its own: the sweep units compile as before
-    ("pht_loglik.hip", (), ())]
+    ("pht_loglik.hip", (), ())] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
-           "pht_loglik_args.h"]
+           "pht_loglik_args.h", "host_internal.h", "host_hip.h", "host_lists.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
 

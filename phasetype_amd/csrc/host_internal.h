@@ -1,0 +1,278 @@
+/*
+ * host_internal.h — what the units of the host runtime share: error
+ * reporting, the R binding, the device context (pht_ctx), the chains group
+ * and the internal functions one unit calls in another.  Nothing here is part
+ * of the C ABI (include/phasetype_amd.h): it all has hidden visibility.
+ *
+ *   host_r.cpp         error text, R runtime and stream, LJMA_Gibbs, R_init_PhaseType
+ *   host_params.cpp    LAPACK binding, eigensystem, the packed parameter block
+ *   host_ctx.cpp       the context: create/destroy/set_obs, the sweep pipeline
+ *   host_chains.cpp    ChainGroup, pht_gibbs_run_chains
+ *   host_rccl.cpp      RCCL binding and its entry points
+ *   host_gibbs.cpp     Gibbs bookkeeping and loop, pht_gibbs_run, pht_theta_to_S
+ *   host_resident.cpp  pht_gibbs_run_resident
+ *   host_loglik.cpp    log-likelihood blocks and pht_ctx_loglik*
+ */
+#ifndef PHT_HOST_INTERNAL_H
+#define PHT_HOST_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+#include <stdint.h>
+
+#include <condition_variable>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/phasetype_amd.h"
+#include "host_hip.h"
+#include "host_lists.h"
+#include "pht_kernels.h"
+#include "pht_layout.h"
+#include "rstream.h"
+
+#pragma GCC visibility push(hidden)
+
+namespace pht {
+namespace host {
+
+static_assert(kUnifRowsCap == kUnifMaxK, "unif_rows caps at the table's last row index");
+
+/* ======================================================= error reporting */
+/* the text behind pht_last_error: one object per thread, shared by every
+ * unit (chain threads hand theirs to the caller, pht_gibbs_run_chains) */
+extern thread_local std::string g_err;
+void set_err(const char *fmt, ...);
+
+#define HIPCHK(x)                                                               \
+  do {                                                                          \
+    hipError_t e_ = (x);                                                        \
+    if (e_ != hipSuccess) {                                                     \
+      ::pht::host::set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return -1;                                                                \
+    }                                                                           \
+  } while (0)
+
+/* ================================================ R runtime (when inside R) */
+struct RHost {
+  typedef double (*unif_fn)(void);
+  typedef double (*rgamma_fn)(double, double);
+  typedef void (*void_fn)(void);
+  typedef void (*printf_fn)(const char *, ...);
+  typedef void (*error_fn)(const char *, ...);
+  bool inR = false;
+  unif_fn unif = nullptr;
+  rgamma_fn rgamma = nullptr;
+  void_fn getrng = nullptr, putrng = nullptr, flush = nullptr;
+  printf_fn rprintf = nullptr;
+  error_fn rerror = nullptr;
+  pht_rstream rs;
+  bool seeded = false;
+  RHost(); /* resolves R's functions when they are in the process */
+  double u() { return inR ? unif() : pht_rs_unif_rand(&rs); }
+  double gamma(double a, double sc) { return inR ? rgamma(a, sc) : pht_rs_rgamma(&rs, a, sc); }
+  void begin() { if (inR) getrng(); }
+  void end() { if (inR) putrng(); }
+};
+RHost &rhost();
+void say(const char *fmt, ...);
+/* a warning the caller must see: Rprintf inside R, stderr otherwise */
+void warn(const char *fmt, ...);
+
+/* a chain's own R-compatible stream (pht_gibbs_run_chains) */
+struct OwnRng {
+  pht_rstream rs;
+  double u() { return pht_rs_unif_rand(&rs); }
+  double gamma(double a, double sc) { return pht_rs_rgamma(&rs, a, sc); }
+};
+
+/* ============================================= parameters (host_params.cpp) */
+bool lapack_ready();
+/* the bound OpenBLAS on one thread for the duration of a scope (the
+ * outermost one sets and restores: a Gibbs run once, a lone eigen() call
+ * per call) */
+struct OneBlasThread {
+  int prev = 0;
+  OneBlasThread();
+  ~OneBlasThread();
+};
+/* evi_out: the eigenvalues' imaginary parts (the log-likelihood refuses a
+ * complex spectrum, pht_loglik_build; the sampler goes on as the reference does) */
+int eigen(int n, const double *S, double *evals, double *Q, double *Qinv, double *evi_out = nullptr);
+int build_params(int n, const double *S, const double *s, int method, std::vector<unsigned char> &out);
+
+/* the reference's precedence MHRS > DCS > ECS (src/PHT_MCMC_Aslett.c:325-337);
+ * the opt-in uniformisation sampler (no reference counterpart) last */
+inline int dispatch_method(int method) {
+  if (method & kMethodMHRS) return kMethodMHRS;
+  if (method & kMethodDCS) return kMethodDCS;
+  if (method & kMethodECS) return kMethodECS;
+  if (method & kMethodUNIF) return kMethodUNIF;
+  return 0;
+}
+
+struct ChainGroup;
+
+}  // namespace host
+}  // namespace pht
+
+/* ========================================================== device context */
+/* Member order is destruction order reversed: the streams come first, so
+ * they are destroyed after every event and buffer below them (as
+ * pht_ctx_destroy always did).  The holder selects the device first. */
+struct pht_ctx {
+  template <class T> using DevBuf = pht::host::DevBuf<T>;
+  template <class T> using PinnedBuf = pht::host::PinnedBuf<T>;
+  using Event = pht::host::Event;
+
+  int device = 0;
+  pht::host::Stream stream;
+  /* ECS: the censored range runs on stream2, concurrently with the exact range */
+  pht::host::Stream stream2;
+  Event evf, evj;
+  int n = 0, method = 0, mhit = 1;
+  /* the reference method asked for (dispatch_method), and the path law of the
+   * UNIF kernels when method is kMethodUNIF: 0 its own, 1 MHRS's / 2 DCS's
+   * law by uniformisation (PHT_MHRS=bridge, PHT_DCS=bridge; pht_unif.h) */
+  int rmethod = 0, ulaw = 0;
+  long count = 0;
+  long n_exact = 0;                      /* exact observations; ECS: positions [0, n_exact) (sorted first) */
+  /* what pht_ctx_set_obs uploads and what is sized by it: replaced as a whole
+   * by the next pht_ctx_set_obs */
+  struct Obs {
+    DevBuf<double> d_y;
+    DevBuf<int> d_cens;
+    DevBuf<uint32_t> d_gid;
+    /* MHRS attempt-search workspace (count * (1 + mhit) tasks) */
+    DevBuf<uint32_t> d_mbest, d_mq0, d_mq1;
+    DevBuf<unsigned> d_mcnt;
+    DevBuf<double> d_utab;               /* UNIF per-sweep table (pht_unif.h) */
+    long utab_cap = 0;                   /* its capacity in doubles */
+    DevBuf<int> d_dcsb;                  /* DCS: per-position end states (dcs_end_kernel) */
+    /* pht_ctx_loglik: the pointwise staging buffer, and the WAIC state per
+     * observation in the device (sorted) order: 5 double arrays
+     * [ref S1 S2 m r] and the counts */
+    DevBuf<double> d_llpw;
+    size_t llpw_cap = 0;
+    DevBuf<double> d_waic;
+    DevBuf<long long> d_wcnt;
+  } obs;
+  DevBuf<unsigned char> d_params;
+  DevBuf<unsigned long long> d_stats;
+  PinnedBuf<unsigned long long> h_stats;
+  PinnedBuf<unsigned char> h_params;
+  std::vector<long> order;               /* sorted position -> local index */
+  std::vector<double> h_ysorted;         /* y in device (sorted) order */
+  double ysum = 0.0;                     /* sum of the shard's y (the fixed-point range check) */
+  double ymax = 0.0;                     /* largest y of the shard (UNIF table length) */
+  /* debug buffers (count observations each): allocated by the first debug
+   * sweep, dropped by pht_ctx_set_obs */
+  struct Dbg {
+    DevBuf<long long> d_zq;
+    DevBuf<int> d_N, d_B, d_pre, d_flags;
+    DevBuf<uint32_t> d_ndraw;
+    long cap = 0;
+  } dbg;
+  float last_ms = 0.f;
+  Event ev0, ev1;
+  pht::host::ChainGroup *grp = nullptr; /* pht_gibbs_run_chains: exact ECS launched with the other chains */
+  int gidx = -1;
+  long long flagged = 0; /* flagged observation-sweeps of the last Gibbs run (node-wide) */
+  long long global_count = -1; /* observations over all shards (pht_ctx_set_global_count) */
+  ncclComm_t comm = nullptr; /* pht_ctx_attach_rccl: stats summed over ranks on `stream` (pht_ctx_destroy ends it) */
+  DevBuf<long long> d_rccl; /* pht_ctx_rccl_prepare: staging buffer of pht_ctx_rccl_allreduce */
+  int rccl_cap = 0;
+  bool stats_zero = false;   /* d_stats zeroed on `stream` after the last sweep's copy */
+  Event evd;                 /* the statistics copy to the host is done */
+  /* the statistics block published by pht_stats_out_kernel: host-pinned
+   * coherent words (mapped: .dev()) + a flag the host polls (empty: the copy
+   * + event path, or PHT_STATS_COPY=1) */
+  PinnedBuf<unsigned long long> h_out;
+  PinnedBuf<unsigned> h_flag;
+  unsigned seq = 0;
+  /* sweeps enqueued and not yet waited for (oldest first): the statistics
+   * flag value each publishes and its kernel-time event pair; two in flight
+   * in the pipelined Gibbs loop (gibbs_run), else one */
+  struct Inflight {
+    unsigned seq = 0, gate = 0;
+    bool timed = false;
+    int evs = 0;
+  } infl[2];
+  int nin = 0;
+  unsigned nenq = 0;
+  Event ev0b, ev1b;
+  /* the pipelined loop's gate (pht_gate_kernel): word 0 the released value
+   * (host writes), word 16 the device's ack; the parameter block staged in
+   * coherent pinned memory for the gate kernel's copy (both mapped) */
+  PinnedBuf<unsigned> h_gate;
+  PinnedBuf<unsigned char> h_pg;
+  unsigned gate_seq = 0;
+  /* pht_ctx_loglik (allocated on first use): draw blocks and totals of a call */
+  DevBuf<double> d_llblk;
+  DevBuf<unsigned long long> d_lltot;
+  long llblk_cap = 0, lltot_cap = 0;
+  int ll_grid_cap = 0;
+};
+
+namespace pht {
+namespace host {
+
+/* ================================================= context (host_ctx.cpp) */
+/* the arguments every sweep launch of context c shares: its buffers, the
+ * Philox key, the sweep number and the per-sweep knobs.  Each caller then
+ * sets only what its launch differs in. */
+SweepArgs sweep_args(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep, int zexp);
+/* ECS exact range: the claim-order knobs the one-context and the chains
+ * launch share (PHT_NEWCAP, PHT_SPREAD; read per sweep) */
+void ecs_claim_knobs(const pht_ctx *c, SweepArgs &ae);
+/* UNIF: a's table fields for a largest lam of lmax, the context's table grown
+ * to hold it (headroom: half as many rows again, for a host loop whose rates
+ * move from sweep to sweep) */
+int unif_table(pht_ctx *c, SweepArgs &a, double lmax, bool headroom);
+int unif_prepare(pht_ctx *c, SweepArgs &a);
+int ctx_launch(pht_ctx *c, const SweepArgs &a, bool debug);
+int ctx_enqueue(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep, int zexp, bool debug, bool timed = true,
+                unsigned gate = 0);
+int ctx_wait(pht_ctx *c);
+void ctx_drain(pht_ctx *c);
+void ctx_release(pht_ctx *c, unsigned gate, const unsigned char *pb, size_t bytes);
+
+/* =============================================== chains (host_chains.cpp) */
+int group_sweep(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep, int zexp);
+
+/* ==================================================== RCCL (host_rccl.cpp) */
+/*
+ * RCCL bound at run time (dlopen), so the library loads where RCCL is absent
+ * (inside R on a single GPU) and only multi-process runs need it.  Replaces
+ * the per-sweep host callback (pht_reduce_fn) with an all-reduce on the device
+ * copy of the statistics block, on the sweep's stream: no host round trip
+ * between the kernels and the sum.  The reference has no distributed mode
+ * (its observation loop is src/PHT_MCMC_Aslett.c:325-337).
+ */
+struct RcclApi {
+  bool ok = false;
+  ncclResult_t (*getUniqueId)(ncclUniqueId *) = nullptr;
+  ncclResult_t (*commInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
+  ncclResult_t (*allReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t,
+                            hipStream_t) = nullptr;
+  ncclResult_t (*commDestroy)(ncclComm_t) = nullptr;
+  const char *(*errStr)(ncclResult_t) = nullptr;
+};
+RcclApi &rccl();
+
+/* ============================================ Gibbs loop (host_gibbs.cpp) */
+/* Run the Gibbs loop over a set of device shards; reduce = optional
+ * cross-process all-reduce of the int64 statistics block.  Rng: RHost or
+ * OwnRng (instantiated in host_gibbs.cpp). */
+template <class Rng>
+int gibbs_run(Rng &R, int it, int method, int n, int m, const double *nu, const double *zeta, const int *T,
+              const double *C, int silent, const double *start, double *res, std::vector<pht_ctx *> &ctxs,
+              uint32_t k0, uint32_t k1, int zexp, pht_reduce_fn reduce, void *reduce_user, double *kernel_ms_total);
+
+}  // namespace host
+}  // namespace pht
+
+#pragma GCC visibility pop
+
+#endif

@@ -24,7 +24,7 @@ PHT_DECL(20)
 #undef PHT_DECL
 
 /* The sweep's statistics block to the host without a copy engine round trip
- * (ctx_enqueue, gibbs_host.cpp): one workgroup reads the block, stores it
+ * (ctx_enqueue, host_ctx.cpp): one workgroup reads the block, stores it
  * into host-pinned coherent memory and zeroes it for the next sweep; after
  * a system-scope fence of every thread, thread 0 publishes seq in the
  * host-visible flag with a release store.  The host polls that flag instead
@@ -47,7 +47,7 @@ extern "C" hipError_t pht_launch_stats_out(unsigned long long *d_stats, unsigned
   return hipGetLastError();
 }
 
-/* The pipelined Gibbs loop's gate (gibbs_host.cpp, gibbs_run): the next
+/* The pipelined Gibbs loop's gate (host_gibbs.cpp, gibbs_run): the next
  * sweep is enqueued while the current one runs, behind this one-workgroup
  * kernel, which waits until the host has written that sweep's parameter
  * block (host-pinned coherent memory) and released `want` in the gate word,

@@ -75,7 +75,7 @@ struct SweepArgs {
 
 /* the device-resident chain's per-sweep update (pht_resident.hip); all
  * pointers are device memory.  Parameter maps (GibbsState's lists,
- * gibbs_host.cpp) as CSR: entries of parameter k at [off[k], off[k+1]) in
+ * host_lists.h) as CSR: entries of parameter k at [off[k], off[k+1]) in
  * insertion order (the update visits them in reverse, as the host does). */
 struct ResidentArgs {
   int n, m, it, init;

@@ -93,7 +93,7 @@ PHT_LHD Layout make_layout(int n) {
  *   flags, uniforms drawn, jumps, Brent CDF evals, UNIF cap hits, 1 spare, and 8 cycle
  *   counters filled only by diagnostic PHT_STAMPS builds */
 constexpr int kStatExtra = 16; /* [8..15]: per-phase cycle stamps (PHT_STAMPS builds) */
-/* extra-word indices read by the host (gibbs_host.cpp) */
+/* extra-word indices read by the host (host_gibbs.cpp) */
 constexpr int kXObs = 0;       /* observations processed: must equal the shard's count */
 constexpr int kXFlagged = 2;   /* observations that hit a cap or guard */
 constexpr int kXUnifCap = 6;   /* UNIF observations past the Poisson table / lam cap: the sweep is an error */

@@ -35,7 +35,7 @@ constexpr int kResThreads = 64;
 constexpr int kResMaxM = (kMaxN + 1) * (kMaxN + 1);
 
 /*
- * ECS/DCS: the spectral part of build_params (gibbs_host.cpp; the
+ * ECS/DCS: the spectral part of build_params (host_params.cpp; the
  * reference's src/PHT_MCMC_Aslett.c:320-332) from this sweep's S, s, P in
  * the parameter block: the eigensystem (include/pht_eigen.h: refined from
  * the previous sweep's, the full QR at init or when that fails) in place of
@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(kResThreads) resident_update_kernel(ResidentAr
     for (int e = r.tl_off[k]; e < r.tl_off[k + 1]; e++) r.TT[r.tl_ij[e]] = theta[k] * r.tl_c[e];
   __syncthreads();
   /* the diagonal: the constructor sums a row forward, the update in reverse
-   * list order (GibbsState, gibbs_host.cpp) */
+   * list order (GibbsState, host_gibbs.cpp) */
   if (tid < n) {
     const int i = tid;
     double d = 0.0;

@@ -75,7 +75,7 @@
  * observation's path is then NOT a draw of the target law (a truncated
  * Poisson sum, or a placeholder path z(0) = y absorbed from state 0), so a
  * sweep with any such observation is an error (statistics word kXUnifCap;
- * gibbs_host.cpp fails the run, the resident update sets err bit 16).
+ * host_gibbs.cpp fails the run, the resident update sets err bit 16).
  */
 #ifndef PHT_UNIF_H
 #define PHT_UNIF_H

@@ -5,7 +5,7 @@
  * (`unif_rand`, `exp_rand`, `norm_rand`, `rgamma`, `runif`, `rexp`, `dexp`;
  * call sites: src/PHT_MCMC_Aslett.c:200,366, src/arms.c:838-846,
  * src/Simulate_AbsCTMC_*.c).  Inside an R process the product library calls
- * R's own functions (resolved at load time, see gibbs_host.cpp); outside R
+ * R's own functions (resolved at load time, see host_r.cpp); outside R
  * (pytest, bench.py, the GPU box) it uses this restatement of R's default
  * generator: Mersenne-Twister with R's `set.seed` scrambling, Ahrens-Dieter
  * (1972) `exp_rand`, inversion `norm_rand` (Wichura AS241) and

@@ -266,7 +266,7 @@ def test_fixed_point_overflow_is_an_error(gpu, method):
 @pytest.mark.parametrize("method", [2, 1, 4])
 def test_published_statistics_equal_the_copy_path(gpu, monkeypatch, method):
     """The statistics block reaches the host through pht_stats_out_kernel
-    (host-pinned words + a polled flag, gibbs_host.cpp ctx_wait) by default;
+    (host-pinned words + a polled flag, host_ctx.cpp ctx_wait) by default;
     PHT_STATS_COPY=1 (read at context creation) takes the copy + event path.
     Several sweeps of a 30 % censored shard: the same block every sweep (the
     published block is also zeroed for the next sweep by the same kernel)."""
@@ -291,7 +291,7 @@ def test_published_statistics_equal_the_copy_path(gpu, monkeypatch, method):
 
 @pytest.mark.parametrize("method", [2, 1, 4])
 def test_pipelined_loop_equals_serial(gpu, monkeypatch, method):
-    """The pipelined Gibbs loop (gibbs_host.cpp gibbs_run: sweep k + 1
+    """The pipelined Gibbs loop (host_gibbs.cpp gibbs_run: sweep k + 1
     enqueued behind pht_gate_kernel while sweep k runs) against the serial
     loop (PHT_PIPELINE=0, read at context creation): the same chain, with the
     censored range's concurrent stream (ECS) and the multi-kernel MHRS sweep.
