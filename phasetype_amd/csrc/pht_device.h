@@ -475,7 +475,7 @@ __device__ __forceinline__ double arms_metropolis(const Env &e, const WPt &p, do
  * iteration), so a wavefront never waits for its longest rejection chain.
  * Draws, evaluations and results are those of arms_loop. */
 struct ArmsPend {
-  double px, py, pey, yprev;
+  double px, py, yprev; /* (no ey of the point: arms_update does not read it) */
   int pr, it; /* it: index of the next iteration */
 };
 
@@ -483,7 +483,7 @@ struct ArmsPend {
 template <class Env, class F>
 __device__ __forceinline__ int arms_step(Env &e, F &f, ArmsPend &pd, double xprev, double &xsamp, Lane &ln) {
   WPt p;
-  p.x = pd.px; p.y = pd.py; p.ey = pd.pey; p.pr = pd.pr;
+  p.x = pd.px; p.y = pd.py; p.ey = 0.0; p.pr = pd.pr;
   arms_update(e, p, f, ln);
   if (pd.it >= kArmsMaxIt) {
     xsamp = xprev;
@@ -496,7 +496,7 @@ __device__ __forceinline__ int arms_step(Env &e, F &f, ArmsPend &pd, double xpre
   const double ynew = f(q.x);
   ln.neval++;
   if (y >= ynew) {
-    pd.px = q.x; pd.py = ynew; pd.pey = expshift(ynew, e.ymax); pd.pr = q.pr;
+    pd.px = q.x; pd.py = ynew; pd.pr = q.pr;
     pd.it++;
     return 1;
   }

@@ -39,6 +39,19 @@ constexpr bool round_env_ok() { return Env::kLds == 0 || Env::kLds >= kRoundCap;
 template <int NT>
 constexpr bool round_lds_only() { return NT > 0 && NT < 20; }
 
+/* The converged blocks see only envelopes that arms() built and
+ * arms_update() grew: 9 points at a jump's start, two more per update, so
+ * there cnt is 9, 11 or 13 and last = cnt - 1 is 8, 10 or 12.  "position p
+ * exists" (p <= last, p a compile-time position) is therefore decided at
+ * compile time for p <= 8 and is otherwise one of two tests, last >= 10 and
+ * last >= 12, shared by every position that asks: the same decisions as
+ * p <= last, without a compare, select or branch per position. */
+constexpr int kRoundMinLast = 8;
+__device__ __forceinline__ bool round_has(int p, int last) {
+  const int pe = (p + 1) & ~1; /* the even position at or above p */
+  return pe <= kRoundMinLast || pe <= last;
+}
+
 /*
  * All intersection points (even positions) of an envelope of at most CAP
  * points (cnt = last + 1), branch-free, with arms_meet's expressions
@@ -77,8 +90,8 @@ __device__ __forceinline__ void round_meets(Env &e, int last) {
 #pragma unroll
   for (int K = 0; K < CAP; K += 2) {
     const int mo = K / 2; /* odd index of position K + 1 */
-    const bool active = (K <= last);
-    const bool il = (K >= 3), ir = (K + 3 <= last), irl = (K >= 1 && K + 1 <= last);
+    const bool active = round_has(K, last);
+    const bool il = (K >= 3), ir = round_has(K + 3, last), irl = (K >= 1 && round_has(K + 1, last));
     double xm1 = 0.0, ym1 = 0.0, xp1 = 0.0, yp1 = 0.0;
     if (K >= 1) { xm1 = e.X(K - 1); ym1 = e.Y(K - 1); }
     if (K + 1 < CAP) { xp1 = e.X(K + 1); yp1 = e.Y(K + 1); }
@@ -139,7 +152,7 @@ __device__ __forceinline__ void round_cumulate(Env &e, double *cs) {
   }
   double ymax = ys[0];
 #pragma unroll
-  for (int k = 1; k < CAP; k++) ymax = (k < cnt && ys[k] > ymax) ? ys[k] : ymax;
+  for (int k = 1; k < CAP; k++) ymax = (round_has(k, cnt - 1) && ys[k] > ymax) ? ys[k] : ymax;
   e.ymax = ymax;
   /* (positions < cnt lie at or below ymax; those beyond are never read) */
   double eyp = expshift_le(ys[0], ymax);
@@ -164,11 +177,12 @@ template <int CAP, bool LD, class Env>
 __device__ __forceinline__ void round_invert(Env &e, const double *cs, double prob, WPt &p) {
   const int last = e.cnt - 1;
   /* cum at last and last - 1 (the segment's ends before the scan moves) */
-  double clast = cs[0], cprev = cs[0];
+  double clast = cs[kRoundMinLast], cprev = cs[kRoundMinLast - 1];
 #pragma unroll
-  for (int k = 1; k < CAP; k++) {
-    clast = (k == last) ? cs[k] : clast;
-    cprev = (k == last) ? cs[k - 1] : cprev;
+  for (int k = kRoundMinLast + 2; k < CAP; k += 2) {
+    const bool h = round_has(k, last);
+    clast = h ? cs[k] : clast;
+    cprev = h ? cs[k - 1] : cprev;
   }
   const double u = prob * clast;
   /* q moves down from last while cum[q-1] > u; the segment's ends follow */
@@ -177,7 +191,7 @@ __device__ __forceinline__ void round_invert(Env &e, const double *cs, double pr
   bool go = true;
 #pragma unroll
   for (int k = CAP - 2; k >= 1; k--) {
-    if (k <= last - 1) {
+    if (round_has(k + 1, last)) {
       go = go && (cs[k] > u);
       q = go ? k : q;
       cr = go ? cs[k] : cr;
@@ -244,7 +258,7 @@ __device__ __forceinline__ void round_insert(Env &e, const ArmsPend &pd, F &f, L
    * value (stores only where it moves) */
 #pragma unroll
   for (int k = 0; k + 2 < CAP; k++) {
-    if (k >= pr && k <= last) {
+    if (k >= pr && round_has(k, last)) {
       e.sX(k + 2, xs[k]);
       e.sY(k + 2, ys[k]);
     }
@@ -445,7 +459,7 @@ __device__ __forceinline__ void ecs_round(const Par<NT> &P, Lane &ln, Env &env, 
   PHT_STAMP(ln, 8);
   if (itr) {
     if (yv >= ynew) {
-      pd.px = q.x; pd.py = ynew; pd.pey = expshift(ynew, env.ymax); pd.pr = q.pr;
+      pd.px = q.x; pd.py = ynew; pd.pr = q.pr;
       pd.it++;
       pend = true;
     } else {

@@ -741,7 +741,7 @@ __device__ __forceinline__ bool row_round(const Par<NT> &P, const RowId<NT> &id,
   PHT_STAMP(ln, 8);
   if (itr) {
     if (yv >= ynew) {
-      pd.px = q.x; pd.py = ynew; pd.pey = expshift(ynew, ev.ymax); pd.pr = q.pr;
+      pd.px = q.x; pd.py = ynew; pd.pr = q.pr;
       pd.it++;
       pend = true;
     } else {

@@ -1169,8 +1169,11 @@ __device__ __forceinline__ void ecs_row_body(const SweepArgs &a, unsigned blk, u
 
 /* waves per SIMD the ECS kernel is compiled for (its DEBUG instantiation,
  * per-observation outputs for the parity tests, is left unconstrained): two
- * at n = 10 with row blocks (the row code would otherwise take it to one)
- * and at n = 15, where the
+ * at n = 10, with or without row blocks: the one-lane body sits a few
+ * registers under the 256 of two waves, and left to itself the allocator
+ * crosses that line on small changes of the round code (258 VGPRs = one wave
+ * per SIMD = +31 % kernel time at cfg4, where asked for two it fits 255
+ * without a spill); two at n = 15, where the
  * W row read from LDS (EcsDens) lets it fit (255 VGPRs, no spills, per the
  * built library's metadata: tools/kernel_regs.py); at n = 20 two as well
  * since the compact parameter prefix lets two blocks share a CU (r04: 43
@@ -1181,7 +1184,7 @@ __device__ __forceinline__ void ecs_row_body(const SweepArgs &a, unsigned blk, u
  * few VGPRs: they are never timed. */
 template <int NT, bool ROWS = false>
 constexpr int ecs_waves() {
-  return PHT_ECS_WAVES > 0 ? PHT_ECS_WAVES : ((NT == 15 || NT == 20 || (ROWS && NT == 10)) ? 2 : 1);
+  return PHT_ECS_WAVES > 0 ? PHT_ECS_WAVES : ((NT == 10 || NT == 15 || NT == 20) ? 2 : 1);
 }
 template <int NT, bool DEBUG, bool ROWS>
 __global__ void __launch_bounds__(kBlock)

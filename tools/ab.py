@@ -15,7 +15,8 @@ A library may carry environment settings for its worker: "a.so@PHT_ECS_OCC=1,PHT
 (the same library twice with different knobs is two variants).
 Each variant runs the bench workload (BD-exit(n), N obs, ECS) as a Gibbs
 run of --sweeps sweeps per round; rounds interleave the variants.  Prints a
-JSON summary: per-variant median / min ms per sweep and kernel ms.
+JSON summary: per-variant median / min ms per sweep and kernel ms, the
+kernel ms of every round and kernel_ms_half_spread.
 Every variant must also reproduce variant 0's Gibbs draws exactly (same
 seed) — the A/B is only meaningful between bit-identical variants.
 """
@@ -131,8 +132,16 @@ def main():
                     print(json.dumps({"error": f"{p} draws differ from {a.libs[0]}"}))
             times[p].append(dt / a.sweeps * 1e3)
             kern[p].append(kms / a.sweeps)
+    def halves(v):
+        """|median of the first half - median of the second half| of a variant's own rounds: the spread
+        a difference between two variants has to exceed"""
+        h = len(v) // 2
+        return float(abs(np.median(v[:h]) - np.median(v[len(v) - h:]))) if h else 0.0
+
     out = {(os.path.basename(_split(p)[0]) + ("@" + p.partition("@")[2] if "@" in p else "")): {"ms_per_sweep_median": float(np.median(times[p])), "ms_min": float(np.min(times[p])),
-                                 "kernel_ms_median": float(np.median(kern[p]))} for p in a.libs}
+                                 "kernel_ms_median": float(np.median(kern[p])),
+                                 "kernel_ms_rounds": [round(float(k), 5) for k in kern[p]],
+                                 "kernel_ms_half_spread": halves(kern[p])} for p in a.libs}
     print(json.dumps(out, indent=1))
     for lb, pr in zip(libs, procs):
         lb.send(None)
