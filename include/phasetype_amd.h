@@ -153,9 +153,11 @@ int pht_gibbs_run_chains(pht_ctx **ctxs, int nchains, const uint32_t *seeds, int
  *   sum over exact y of log f(y) + sum over censored y of log Fbar(y),
  * evaluated on the GPU from the draw's eigensystem over the context's resident
  * observations; arithmetic and layouts are specified in include/pht_loglik.h.
- * SPECTRAL ONLY: a draw whose spectrum is complex or defective (dgeevx info,
- * a non-zero imaginary part, a non-finite coefficient) gets a non-zero flag
- * word, is never evaluated, and reads NaN.
+ * This (default) evaluator is SPECTRAL: a draw whose spectrum is complex or
+ * defective (dgeevx info, a non-zero imaginary part, a non-finite coefficient)
+ * gets a non-zero flag word, is never evaluated, and reads NaN.  Such draws
+ * are served by the second evaluator, by uniformisation (pht_ctx_loglik_unif
+ * below; include/pht_loglik_unif.h).
  *
  * pht_loglik_build: host only (no GPU), one draw's block of pht_loglik_bytes(n)
  *   bytes; returns 0, the positive flag word of an unusable draw, < 0 on error.
@@ -181,6 +183,27 @@ int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batc
                    double *pointwise, int accumulate);
 int pht_ctx_loglik_reset(pht_ctx *c);
 int pht_ctx_loglik_state(pht_ctx *c, double *ref, double *S1, double *S2, double *m, double *r, int *cnt);
+
+/* The same log-likelihood by uniformisation (include/pht_loglik_unif.h): sums
+ * of non-negative terms straight from (S, s), no eigensystem and no LAPACK, so
+ * it serves complex and defective spectra and does not lose cond(Q) ulps.
+ * Limits: pi = e_1; the table cap of 2047 rows, roughly mu y <= 1500 with
+ * mu = max_i -S_ii; a Poisson-weighted sum below 2^-900.  Beyond either the
+ * observation is bad for that draw (counted in nbad), as in pht_ctx_loglik.
+ *
+ * pht_ctx_loglik_unif: ndraws draws, S the column-major n x n generators one
+ *   after another, s the n-vectors; batch, totals, pointwise and accumulate as
+ *   in pht_ctx_loglik, and the WAIC state is the same one: calls of either
+ *   kind with accumulate continue it in call order.  flags_out: NULL, or
+ *   ndraws flag words (0 = evaluated; PHT_LL_F_NONFINITE 4: a non-finite entry;
+ *   PHT_LL_F_MU 8: mu not positive and finite); a flagged draw is skipped like
+ *   a flagged block.  The tables live in a buffer of their own: a UNIF
+ *   (method 8) context's chain is not affected.
+ * pht_ctx_loglik_unif_K: the last table row K the context would use for a
+ *   draw with this mu (from its largest observation), < 0 on error. */
+int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s, int batch, long long *totals,
+                        double *pointwise, int accumulate, int *flags_out);
+int pht_ctx_loglik_unif_K(pht_ctx *c, double mu);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,8 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains", "PhaseTypeError", "METHODS",
-           "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S"]
+           "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S",
+           "EVALUATORS", "evaluator_runs"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -53,7 +54,7 @@ EXPORTS = [
     "pht_gibbs_run_resident",
     "pht_gibbs_run_chains", "pht_rccl_unique_id", "pht_ctx_rccl_prepare", "pht_ctx_attach_rccl", "pht_ctx_rccl_allreduce",
     "pht_loglik_bytes", "pht_loglik_build", "pht_theta_to_S", "pht_ctx_loglik", "pht_ctx_loglik_reset",
-    "pht_ctx_loglik_state",
+    "pht_ctx_loglik_state", "pht_ctx_loglik_unif", "pht_ctx_loglik_unif_K",
 ]
 
 
@@ -139,6 +140,8 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_loglik.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _lp, C.c_void_p, C.c_int]
     L.pht_ctx_loglik_reset.argtypes = [C.c_void_p]
     L.pht_ctx_loglik_state.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
+    L.pht_ctx_loglik_unif.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _lp, C.c_void_p, C.c_int, _ip]
+    L.pht_ctx_loglik_unif_K.argtypes = [C.c_void_p, C.c_double]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -352,12 +355,82 @@ class Sweeper:
             out["pointwise"] = pw
         return out
 
-    def loglik(self, S_list, s_list, batch: int = 64, pointwise: bool = False, accumulate: bool = False):
+    def loglik_unif(self, S_list, s_list, batch: int = 64, pointwise: bool = False, accumulate: bool = False):
+        """pht_ctx_loglik_unif: the log-likelihood of each draw (S, s) over
+        this shard by uniformisation (include/pht_loglik_unif.h): any finite
+        generator, complex and defective spectra included, no LAPACK.
+
+        The result is ``loglik_blocks``'s dict; ``bad_draw`` marks a draw with
+        a non-finite entry or without a positive finite rate, ``flags`` holds
+        the flag words.  An observation beyond the table (mu y above roughly
+        1500) or below 2^-900 is bad for that draw (``nbad``, total -inf).
+        ``accumulate`` continues the same WAIC state as ``loglik_blocks``."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd = S_all.shape[0]
+        if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
+            raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
+        tot = np.zeros(4 * nd, np.int64)
+        flags = np.zeros(nd, np.int32)
+        pw = np.full((nd, self.count), np.nan) if pointwise else None
+        if self.L.pht_ctx_loglik_unif(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), int(batch), tot,
+                                      pw.ctypes.data if pointwise else None, int(bool(accumulate)), flags) != 0:
+            raise _err(self.L)
+        tot = tot.reshape(nd, 4)
+        bad_draw = flags != 0
+        out = dict(H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(),
+                   bad_draw=bad_draw, flags=flags)
+        out["total"] = loglik_total(out["H"], out["F"], out["nbad"], bad_draw)
+        if pointwise:
+            out["pointwise"] = pw
+        return out
+
+    def loglik_unif_K(self, mu: float) -> int:
+        """The last table row K this context's observations give a draw with
+        largest rate ``mu`` (pht_ctx_loglik_unif_K; at most 2047)."""
+        K = self.L.pht_ctx_loglik_unif_K(self.ctx, float(mu))
+        if K < 0:
+            raise _err(self.L)
+        return K
+
+    def loglik(self, S_list, s_list, batch: int = 64, pointwise: bool = False, accumulate: bool = False,
+               evaluator: str = "spectral", blocks=None):
         """Observed-data log-likelihood of each draw (S, s) over this shard:
-        sum of log f(y) over exact and log Fbar(y) over censored observations
-        (include/pht_loglik.h); see loglik_blocks for the result."""
-        blocks = np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)])
-        return self.loglik_blocks(blocks, batch=batch, pointwise=pointwise, accumulate=accumulate)
+        sum of log f(y) over exact and log Fbar(y) over censored observations;
+        see loglik_blocks for the result, which gains ``evaluator``: per draw,
+        "spectral" or "unif".
+
+        ``evaluator``: "spectral" (the default; include/pht_loglik.h: a draw
+        with a complex or defective spectrum is NaN), "unif" (every draw by
+        uniformisation, include/pht_loglik_unif.h) or "auto" (spectral where
+        the draw's block is usable, uniformisation where its spectrum is
+        complex or defective, NaN only for a non-finite generator).  "auto"
+        issues one call per maximal run of draws of one evaluator, in draw
+        order, so the WAIC state sees the draws in their order.
+        ``blocks``: the draws' spectral blocks where the caller has them."""
+        if evaluator not in EVALUATORS:
+            raise ValueError(f"evaluator must be one of {EVALUATORS}, got {evaluator!r}")
+        S_list, s_list = list(S_list), list(s_list)
+        kw = dict(batch=batch, pointwise=pointwise, accumulate=accumulate)
+        if evaluator == "unif":
+            out = self.loglik_unif(S_list, s_list, **kw)
+            out["evaluator"] = np.full(len(S_list), "unif")
+            return out
+        if blocks is None:
+            blocks = np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)])
+        if evaluator == "spectral":
+            out = self.loglik_blocks(blocks, **kw)
+            out["evaluator"] = np.full(len(S_list), "spectral")
+            return out
+        flags = np.ascontiguousarray(blocks[:, :8]).view(np.uint64).reshape(-1)
+        parts = []
+        for lo, hi, unif in evaluator_runs(flags):
+            r = (self.loglik_unif(S_list[lo:hi], s_list[lo:hi], **kw) if unif
+                 else self.loglik_blocks(blocks[lo:hi], **kw))
+            r.pop("flags", None)
+            r["evaluator"] = np.full(hi - lo, "unif" if unif else "spectral")
+            parts.append(r)
+        return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
     def waic_reset(self) -> None:
         """Forget the per-observation WAIC state (pht_ctx_loglik_reset)."""
@@ -546,8 +619,31 @@ def phtMCMC(x, states, beta, nu, zeta, n, mhit=1, resume=None, silent=False, col
 # ------------------------------------------------- log-likelihood of the draws
 # No reference counterpart: the reference returns the draws only.  The
 # arithmetic is specified in include/pht_loglik.h and runs in
-# phasetype_amd/csrc/pht_loglik.hip; spectral evaluation only (a draw with a
-# complex or defective spectrum is reported as NaN and never evaluated).
+# phasetype_amd/csrc/pht_loglik.hip: the spectral evaluator, the default (a
+# draw with a complex or defective spectrum is reported as NaN and never
+# evaluated).  The second evaluator, by uniformisation, serves those draws:
+# include/pht_loglik_unif.h, phasetype_amd/csrc/pht_loglik_unif.hip.
+EVALUATORS = ("spectral", "unif", "auto")
+LL_F_INFO, LL_F_COMPLEX, LL_F_NONFINITE, LL_F_MU = 1, 2, 4, 8  # flag words (pht_loglik.h, pht_loglik_unif.h)
+
+
+def evaluator_runs(flags) -> list:
+    """evaluator="auto": the draw sequence split into maximal runs of one
+    evaluator, in order, as [(lo, hi, unif)] over draws [lo, hi).  ``flags``:
+    the draws' spectral block flag words.  A draw goes to uniformisation where
+    its spectrum is complex or defective (LL_F_COMPLEX, LL_F_INFO) and its
+    generator finite; otherwise to the spectral evaluator (flag 0: evaluated;
+    LL_F_NONFINITE: NaN from either)."""
+    flags = np.asarray(flags).astype(np.uint64).reshape(-1)
+    unif = ((flags & np.uint64(LL_F_INFO | LL_F_COMPLEX)) != 0) & ((flags & np.uint64(LL_F_NONFINITE)) == 0)
+    runs, lo = [], 0
+    for k in range(1, len(unif) + 1):
+        if k == len(unif) or unif[k] != unif[lo]:
+            runs.append((lo, k, bool(unif[lo])))
+            lo = k
+    return runs
+
+
 def loglik_block(S, s) -> np.ndarray:
     """One draw's block for ``Sweeper.loglik_blocks`` (pht_loglik_build; host
     only): uint8[pht_loglik_bytes(n)].  An unusable draw (complex or defective
@@ -609,9 +705,9 @@ def theta_to_S(theta, T, C_=None):
     return S.reshape(n, n, order="F"), s
 
 
-def _chain_blocks(res, TT_or_T, C_, n, collation="C"):
-    """(blocks uint8 [draws, bytes], n) for the rows of a chain: ``res`` is the
-    dict phtMCMC2 / phtMCMC return or the it x m array of Sweeper.gibbs."""
+def _chain_draws(res, TT_or_T, C_, n, collation="C"):
+    """(S_list, s_list, n) for the rows of a chain: ``res`` is the dict
+    phtMCMC2 / phtMCMC return or the it x m array of Sweeper.gibbs."""
     if isinstance(res, dict):
         samples = np.asarray(res["samples"], np.float64)
         if TT_or_T is None:
@@ -626,8 +722,14 @@ def _chain_blocks(res, TT_or_T, C_, n, collation="C"):
         raise ValueError("the variables of the chain do not match the variables in the generator")
     if samples.shape[1] != int(T.max()):
         raise ValueError(f"the chain has {samples.shape[1]} columns, the generator {int(T.max())} variables")
-    blocks = np.stack([loglik_block(*theta_to_S(row, T, C_)) for row in samples])
-    return blocks, T.shape[0] - 1
+    draws = [theta_to_S(row, T, C_) for row in samples]
+    return [d[0] for d in draws], [d[1] for d in draws], T.shape[0] - 1
+
+
+def _chain_blocks(res, TT_or_T, C_, n, collation="C"):
+    """(blocks uint8 [draws, bytes], n) for the rows of a chain (_chain_draws)."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    return np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)]), n
 
 
 def _obs_sweeper(x, censored, n, device):
@@ -637,17 +739,19 @@ def _obs_sweeper(x, censored, n, device):
 
 
 def log_lik(res, x, TT_or_T=None, censored=None, C_=None, n=None, device: int = 0, batch: int = 64,
-            collation: str = "C") -> np.ndarray:
+            collation: str = "C", evaluator: str = "spectral") -> np.ndarray:
     """The observed-data log-likelihood trace of a chain: one value per row of
     ``res`` (the dict phtMCMC2 / phtMCMC return, or the array of
     Sweeper.gibbs), over data ``x`` / ``censored``.  ``TT_or_T``: the matrix of
     variable names given to phtMCMC2 (numbered as it numbers them; default the
     chain's own) or the integer matrix T of Sweeper.gibbs.  NaN for a draw with
-    a complex or defective spectrum, -inf where an observation has no density."""
-    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    a complex or defective spectrum, -inf where an observation has no density.
+    ``evaluator`` (Sweeper.loglik): "unif" or "auto" evaluate the draws with a
+    complex or defective spectrum too, by uniformisation."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
     sw = _obs_sweeper(x, censored, n, device)
     try:
-        return sw.loglik_blocks(blocks, batch=batch)["total"]
+        return sw.loglik(S_list, s_list, batch=batch, evaluator=evaluator)["total"]
     finally:
         sw.close()
 
@@ -665,15 +769,18 @@ def waic_from_state(st) -> dict:
 
 
 def waic(res, x, TT_or_T=None, censored=None, C_=None, n=None, burn: int = 0, device: int = 0, batch: int = 64,
-         collation: str = "C") -> dict:
+         collation: str = "C", evaluator: str = "spectral") -> dict:
     """WAIC of a chain (rows from ``burn`` on) over data ``x`` / ``censored``:
     dict(elpd_waic, p_waic, lppd, waic, pointwise=(lppd_i, p_waic_i),
-    n_draws_used).  Draws with a complex or defective spectrum are left out."""
-    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    n_draws_used).  Draws with a complex or defective spectrum are left out by
+    the default ``evaluator``; "auto" (Sweeper.loglik) evaluates them by
+    uniformisation, in the chain's order, and n_draws_used then counts every
+    finite draw."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
     sw = _obs_sweeper(x, censored, n, device)
     try:
         sw.waic_reset()
-        r = sw.loglik_blocks(blocks[int(burn):], batch=batch, accumulate=True)
+        r = sw.loglik(S_list[int(burn):], s_list[int(burn):], batch=batch, accumulate=True, evaluator=evaluator)
         out = waic_from_state(sw.waic_state())
         out["n_draws_used"] = int(np.sum(~r["bad_draw"]))
         return out
@@ -681,18 +788,22 @@ def waic(res, x, TT_or_T=None, censored=None, C_=None, n=None, burn: int = 0, de
         sw.close()
 
 
-def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int = 64, collation: str = "C") -> dict:
+def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int = 64, collation: str = "C",
+              evaluator: str = "spectral") -> dict:
     """Per-draw curves on ``grid``: dict(logdens, logsurv, hazard), each
     [draws, len(grid)] (the grid as exact, then as censored observations, in
-    pointwise mode).  Bands: ``np.quantile(out["hazard"], [.025, .975], axis=0)``."""
-    blocks, n = _chain_blocks(res, TT_or_T, C_, n, collation)
+    pointwise mode).  Bands: ``np.quantile(out["hazard"], [.025, .975], axis=0)``.
+    ``evaluator``: as in Sweeper.loglik."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    blocks = None if evaluator == "unif" else np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)])
     grid = np.ascontiguousarray(grid, np.float64)
     sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    kw = dict(batch=batch, pointwise=True, evaluator=evaluator, blocks=blocks)
     try:
         sw.set_obs(grid, np.zeros(len(grid), np.int32))
-        ld = sw.loglik_blocks(blocks, batch=batch, pointwise=True)["pointwise"]
+        ld = sw.loglik(S_list, s_list, **kw)["pointwise"]
         sw.set_obs(grid, np.ones(len(grid), np.int32))
-        ls = sw.loglik_blocks(blocks, batch=batch, pointwise=True)["pointwise"]
+        ls = sw.loglik(S_list, s_list, **kw)["pointwise"]
     finally:
         sw.close()
     return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))

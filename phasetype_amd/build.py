@@ -3,7 +3,8 @@
 hipcc for gfx950: the HIP kernels (pht_kernels_nt.hip once per compile-time
 n, in parallel, + the pht_dispatch.hip launcher), the host runtime / C ABI
 (the host_*.cpp units, csrc/host_internal.h), the R-compatible stream
-(rstream.c) and the log-likelihood kernel (pht_loglik.hip), then one link.
+(rstream.c) and the log-likelihood kernels (pht_loglik.hip spectral,
+pht_loglik_unif.hip by uniformisation), then one link.
 ``-ffp-contract=off`` is required: the device path must reproduce the
 oracle's arithmetic bit for bit (no implicit FMA contraction anywhere).
 """
@@ -44,11 +45,13 @@ UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT
          for k in KERNEL_NTS] + [
     ("pht_dispatch.hip", (), ()), ("pht_resident.hip", (), ()),
     # the log-likelihood kernel (include/pht_loglik.h), a unit of its own: the sweep units compile as before
-    ("pht_loglik.hip", (), ())] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
+    ("pht_loglik.hip", (), ()),
+    # its second evaluator, by uniformisation (include/pht_loglik_unif.h), again a unit of its own
+    ("pht_loglik_unif.hip", (), ())] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
-           "pht_loglik_args.h", "host_internal.h", "host_hip.h", "host_lists.h"]
+           "pht_loglik_args.h", "pht_loglik_unif_args.h", "host_internal.h", "host_hip.h", "host_lists.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
 
@@ -65,7 +68,8 @@ def inputs() -> list:
     script with its flags)."""
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
     deps += [os.path.join(REPO, "include", f) for f in ("phasetype_amd.h", "pht_detmath.h", "pht_philox.h",
-                                                          "pht_gamma.h", "pht_eigen.h", "pht_loglik.h")]
+                                                          "pht_gamma.h", "pht_eigen.h", "pht_loglik.h",
+                                                          "pht_loglik_unif.h")]
     deps.append(os.path.abspath(__file__))
     return deps
 

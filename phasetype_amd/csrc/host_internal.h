@@ -11,7 +11,7 @@
  *   host_rccl.cpp      RCCL binding and its entry points
  *   host_gibbs.cpp     Gibbs bookkeeping and loop, pht_gibbs_run, pht_theta_to_S
  *   host_resident.cpp  pht_gibbs_run_resident
- *   host_loglik.cpp    log-likelihood blocks and pht_ctx_loglik*
+ *   host_loglik.cpp    log-likelihood blocks, pht_ctx_loglik* and pht_ctx_loglik_unif*
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -213,6 +213,10 @@ struct pht_ctx {
   DevBuf<unsigned long long> d_lltot;
   long llblk_cap = 0, lltot_cap = 0;
   int ll_grid_cap = 0;
+  /* pht_ctx_loglik_unif: a call's (S, s, meta words) and one batch's tables
+   * [draw][k][2]; its own buffer, never the sampler's obs.d_utab */
+  DevBuf<double> d_lluin, d_llutab;
+  size_t lluin_cap = 0, llutab_cap = 0;
 };
 
 namespace pht {

@@ -2,11 +2,13 @@
  * host_loglik.cpp — log-likelihood of posterior draws.
  *
  * No reference counterpart: the reference returns the draws and nothing
- * else.  Specification in include/pht_loglik.h; the kernel is
- * pht_loglik.hip.  Spectral evaluation only: a draw whose spectrum is complex
- * (the sampler warns and uses the real parts, as the reference does), whose
- * LAPACK call fails or whose coefficients are not finite is flagged and never
- * evaluated.
+ * else.  Two evaluators, chosen per call.  Spectral (specification in
+ * include/pht_loglik.h, kernel pht_loglik.hip; pht_loglik_build +
+ * pht_ctx_loglik): a draw whose spectrum is complex (the sampler warns and
+ * uses the real parts, as the reference does), whose LAPACK call fails or
+ * whose coefficients are not finite is flagged and never evaluated.
+ * Uniformisation (include/pht_loglik_unif.h, pht_loglik_unif.hip;
+ * pht_ctx_loglik_unif): any finite generator, straight from (S, s), no LAPACK.
  */
 #include <math.h>
 #include <string.h>
@@ -16,6 +18,8 @@
 #include "host_internal.h"
 #include "pht_loglik.h"
 #include "pht_loglik_args.h"
+#include "pht_loglik_unif.h"
+#include "pht_loglik_unif_args.h"
 
 using namespace pht;
 using namespace pht::host;
@@ -137,29 +141,35 @@ static int loglik_need_obs(pht_ctx *c, const char *who) {
   return 0;
 }
 
-extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
-                              double *pointwise, int accumulate) {
-  if (loglik_need_obs(c, "pht_ctx_loglik")) return -1;
-  if (ndraws < 1 || !blocks || !totals || batch < 1 || batch > kLoglikBatch) {
-    set_err("pht_ctx_loglik: need ndraws >= 1, blocks, totals and 1 <= batch <= %d", kLoglikBatch);
-    return -1;
-  }
-  HIPCHK(hipSetDevice(c->device));
+/* where a launch of either evaluator puts its results */
+struct LoglikOut {
+  unsigned long long *totals; /* the launch's first draw */
+  double *pw;
+  int acc;
+  double *w_ref, *w_S1, *w_S2, *w_m, *w_r;
+  long long *w_cnt;
+};
+
+/* What a call of either evaluator does around its launches: the totals, the
+ * pointwise staging buffer and the WAIC state (shared by both, so calls of
+ * either kind with `accumulate` continue one state), the batches in draw
+ * order, the pointwise rows back in the caller's observation order, the
+ * device time of the call.  launch(d0, nb, out) enqueues draws [d0, d0 + nb)
+ * on the context's stream. */
+template <class Launch>
+static int loglik_batches(pht_ctx *c, int ndraws, int batch, long long *totals, double *pointwise, int accumulate,
+                          Launch launch) {
   hipStream_t st = c->stream.get();
-  ctx_drain(c);
-  const int n = c->n, words = pht_ll_words(n);
   const long count = c->count;
   if (!c->ll_grid_cap) {
     int cus = 0;
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     c->ll_grid_cap = std::max(1, cus) * 4;
   }
-  HIPCHK(ensure(c->d_llblk, c->llblk_cap, (size_t)ndraws * words));
   HIPCHK(ensure(c->d_lltot, c->lltot_cap, (size_t)ndraws * PHT_LL_TOT));
   const int bmax = std::min(batch, ndraws);
   if (pointwise) HIPCHK(ensure(c->obs.d_llpw, c->obs.llpw_cap, (size_t)bmax * (size_t)count));
   if (accumulate && loglik_waic(c, false)) return -1;
-  HIPCHK(hipMemcpyAsync(c->d_llblk.get(), blocks, 8 * (size_t)ndraws * words, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(c->d_lltot.get(), 0, sizeof(unsigned long long) * (size_t)ndraws * PHT_LL_TOT, st));
   std::vector<double> hpw;
   if (pointwise) hpw.resize((size_t)bmax * (size_t)count);
@@ -168,25 +178,19 @@ extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *block
   HIPCHK(hipEventRecord(c->ev0.get(), st));
   for (int d0 = 0; d0 < ndraws; d0 += batch) {
     const int nb = std::min(batch, ndraws - d0);
-    LoglikArgs a{};
-    a.n = n;
-    a.nd = nb;
-    a.count = count;
-    a.y = c->obs.d_y.get();
-    a.cens = c->obs.d_cens.get();
-    a.blocks = c->d_llblk.get() + (size_t)d0 * words;
-    a.totals = c->d_lltot.get() + (size_t)d0 * PHT_LL_TOT;
-    a.pw = pointwise ? c->obs.d_llpw.get() : nullptr;
-    a.acc = accumulate ? 1 : 0;
+    LoglikOut o{};
+    o.totals = c->d_lltot.get() + (size_t)d0 * PHT_LL_TOT;
+    o.pw = pointwise ? c->obs.d_llpw.get() : nullptr;
+    o.acc = accumulate ? 1 : 0;
     if (accumulate) {
-      a.w_ref = c->obs.d_waic.get();
-      a.w_S1 = c->obs.d_waic.get() + count;
-      a.w_S2 = c->obs.d_waic.get() + 2 * count;
-      a.w_m = c->obs.d_waic.get() + 3 * count;
-      a.w_r = c->obs.d_waic.get() + 4 * count;
-      a.w_cnt = c->obs.d_wcnt.get();
+      o.w_ref = c->obs.d_waic.get();
+      o.w_S1 = c->obs.d_waic.get() + count;
+      o.w_S2 = c->obs.d_waic.get() + 2 * count;
+      o.w_m = c->obs.d_waic.get() + 3 * count;
+      o.w_r = c->obs.d_waic.get() + 4 * count;
+      o.w_cnt = c->obs.d_wcnt.get();
     }
-    HIPCHK(pht_launch_loglik(&a, c->ll_grid_cap, st));
+    if (launch(d0, nb, o)) return -1;
     if (pointwise) {
       HIPCHK(hipMemcpyAsync(hpw.data(), c->obs.d_llpw.get(), sizeof(double) * (size_t)nb * (size_t)count,
                             hipMemcpyDeviceToHost, st));
@@ -204,6 +208,116 @@ extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *block
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0.get(), c->ev1.get()));
   return 0;
+}
+
+extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
+                              double *pointwise, int accumulate) {
+  if (loglik_need_obs(c, "pht_ctx_loglik")) return -1;
+  if (ndraws < 1 || !blocks || !totals || batch < 1 || batch > kLoglikBatch) {
+    set_err("pht_ctx_loglik: need ndraws >= 1, blocks, totals and 1 <= batch <= %d", kLoglikBatch);
+    return -1;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream.get();
+  ctx_drain(c);
+  const int n = c->n, words = pht_ll_words(n);
+  HIPCHK(ensure(c->d_llblk, c->llblk_cap, (size_t)ndraws * words));
+  HIPCHK(hipMemcpyAsync(c->d_llblk.get(), blocks, 8 * (size_t)ndraws * words, hipMemcpyHostToDevice, st));
+  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, [&](int d0, int nb, const LoglikOut &o) {
+    LoglikArgs a{};
+    a.n = n;
+    a.nd = nb;
+    a.count = c->count;
+    a.y = c->obs.d_y.get();
+    a.cens = c->obs.d_cens.get();
+    a.blocks = c->d_llblk.get() + (size_t)d0 * words;
+    a.totals = o.totals;
+    a.pw = o.pw;
+    a.acc = o.acc;
+    a.w_ref = o.w_ref;
+    a.w_S1 = o.w_S1;
+    a.w_S2 = o.w_S2;
+    a.w_m = o.w_m;
+    a.w_r = o.w_r;
+    a.w_cnt = o.w_cnt;
+    HIPCHK(pht_launch_loglik(&a, c->ll_grid_cap, st));
+    return 0;
+  });
+}
+
+extern "C" int pht_ctx_loglik_unif_K(pht_ctx *c, double mu) {
+  if (loglik_need_obs(c, "pht_ctx_loglik_unif_K")) return -1;
+  if (!(mu > 0.0) || !std::isfinite(mu)) {
+    set_err("pht_ctx_loglik_unif_K: mu must be positive and finite");
+    return -1;
+  }
+  return pht_llu_K(mu, c->ymax);
+}
+
+extern "C" int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s, int batch,
+                                   long long *totals, double *pointwise, int accumulate, int *flags_out) {
+  if (loglik_need_obs(c, "pht_ctx_loglik_unif")) return -1;
+  if (ndraws < 1 || !S || !s || !totals || batch < 1 || batch > kLoglikBatch) {
+    set_err("pht_ctx_loglik_unif: need ndraws >= 1, S, s, totals and 1 <= batch <= %d", kLoglikBatch);
+    return -1;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream.get();
+  ctx_drain(c);
+  const int n = c->n;
+  /* the draws' meta words (flags, mu, K from the shard's largest y); the table
+   * buffer holds one batch: every draw at the stride of the call's largest K */
+  std::vector<double> meta((size_t)ndraws * PHT_LLU_META);
+  int Kcall = 0;
+  for (int d = 0; d < ndraws; d++) {
+    double *m = meta.data() + (size_t)d * PHT_LLU_META;
+    const unsigned flag = pht_llu_meta(n, S + (size_t)d * n * n, s + (size_t)d * n, c->ymax, m);
+    if (flags_out) flags_out[d] = (int)flag;
+    Kcall = std::max(Kcall, (int)m[PHT_LLU_M_K]);
+  }
+  const int stride = 2 * (Kcall + 1);
+  const int bmax = std::min(batch, ndraws);
+  const size_t nS = (size_t)ndraws * n * n, ns = (size_t)ndraws * n;
+  HIPCHK(ensure(c->d_lluin, c->lluin_cap, nS + ns + meta.size()));
+  HIPCHK(ensure(c->d_llutab, c->llutab_cap, (size_t)bmax * stride));
+  double *dS = c->d_lluin.get(), *ds = dS + nS, *dmeta = ds + ns;
+  HIPCHK(hipMemcpyAsync(dS, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ds, s, sizeof(double) * ns, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dmeta, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice, st));
+  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, [&](int d0, int nb, const LoglikOut &o) {
+    int Kmax = 0;
+    for (int d = d0; d < d0 + nb; d++) Kmax = std::max(Kmax, (int)meta[(size_t)d * PHT_LLU_META + PHT_LLU_M_K]);
+    LlunifTableArgs t{};
+    t.n = n;
+    t.nd = nb;
+    t.S = dS + (size_t)d0 * n * n;
+    t.s = ds + (size_t)d0 * n;
+    t.meta = dmeta + (size_t)d0 * PHT_LLU_META;
+    t.tab = c->d_llutab.get();
+    t.stride = stride;
+    HIPCHK(pht_launch_llunif_table(&t, st));
+    LlunifArgs a{};
+    a.nd = nb;
+    a.Kmax = Kmax;
+    a.count = c->count;
+    a.y = c->obs.d_y.get();
+    a.cens = c->obs.d_cens.get();
+    a.meta = t.meta;
+    a.tab = t.tab;
+    a.stride = stride;
+    a.totals = o.totals;
+    a.pw = o.pw;
+    a.acc = o.acc;
+    a.w_ref = o.w_ref;
+    a.w_S1 = o.w_S1;
+    a.w_S2 = o.w_S2;
+    a.w_m = o.w_m;
+    a.w_r = o.w_r;
+    a.w_cnt = o.w_cnt;
+    /* (under 64 KB of LDS a block: two blocks a CU, half the spectral kernel's cap) */
+    HIPCHK(pht_launch_llunif(&a, std::max(1, c->ll_grid_cap / 2), st));
+    return 0;
+  });
 }
 
 extern "C" int pht_ctx_loglik_reset(pht_ctx *c) {
