@@ -205,6 +205,46 @@ int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s
                         double *pointwise, int accumulate, int *flags_out);
 int pht_ctx_loglik_unif_K(pht_ctx *c, double mu);
 
+/* Posterior-predictive replicates (include/pht_predict.h): for each draw
+ * (S, s), nrep absorption times of PH(e_1, S) simulated forward on the GPU, and
+ * their exact integer reductions.  Limits: pi = e_1; a recorded time below
+ * 2^20; at most 2^22 replicates per draw and call (more: further calls with
+ * rep0 moved on; the words add); at most 1024 edges.
+ *
+ * pht_pred_words: the int64 words per draw (8):
+ *   [Hy, Fy, Hq, Fq, ndone, nbad, nsurv, njump]: sum y = Hy + Fy 2^-32 and
+ *   sum y^2 = Hq + Fq 2^-32 over the ndone recorded replicates, nsurv of them
+ *   stopped at the horizon (recorded as y = horizon), njump their jumps; nbad
+ *   replicates exceeded max_jumps or gave y >= 2^20 and are left out.
+ * pht_pred_table_words(n): the doubles of one draw's table, n + n n.
+ * pht_pred_build: host only (no GPU), one draw's table [scale n][cum n x n];
+ *   returns 0 or the positive flag word of an unusable draw (PHT_LL_F_NONFINITE
+ *   4: a non-finite entry; PHT_LL_F_MU 8: a diagonal not negative and finite;
+ *   16: a negative rate; 32: absorption not certain from state 1; the table is
+ *   then zero), < 0 on error.
+ * pht_ctx_predict: nd draws (S, s as in pht_ctx_loglik_unif), `batch` (1..64)
+ *   per launch, on the context's stream; any method's context, no observations
+ *   needed; its buffers are its own, so the context's chain is not affected.
+ *   Replicate r of draw d draws from the Philox stream (k0, k1; obs rep0 + r,
+ *   a tag no sampler uses, sweep draw0 + d): a replicate's value depends on
+ *   its numbers alone, never on nrep, batch or the grid.  horizon: +inf, or
+ *   the time at which a path is stopped.  max_jumps: 1..2^20.  edges: ne
+ *   strictly increasing finite values (ne = 0: none).
+ *   words_out nd x 8; counts_out nd x (ne + 1), bin = the number of edges <= y;
+ *   ymin_out / ymax_out nd (+inf / -inf where ndone = 0); all exact, so
+ *   replicate ranges, batches and ranks combine by sum, min and max.
+ *   y_out / njump_out: both NULL, or nd x nrep each (pointwise mode; NaN for a
+ *   bad replicate and for a flagged draw).  flags_out: NULL or nd flag words as
+ *   pht_pred_build returns; a flagged draw is skipped, its words stay 0.
+ *   pht_ctx_last_kernel_ms then gives the device time of the call's launches. */
+int pht_pred_words(void);
+int pht_pred_table_words(int n);
+int pht_pred_build(int n, const double *S, const double *s, double *tab, int tab_words);
+int pht_ctx_predict(pht_ctx *c, int nd, const double *S, const double *s, int nrep, long long rep0, unsigned draw0,
+                    unsigned k0, unsigned k1, double horizon, int max_jumps, int ne, const double *edges, int batch,
+                    long long *words_out, long long *counts_out, double *ymin_out, double *ymax_out, double *y_out,
+                    int *njump_out, int *flags_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,8 @@ from . import build as _build
 
 __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains", "PhaseTypeError", "METHODS",
            "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S",
-           "EVALUATORS", "evaluator_runs"]
+           "EVALUATORS", "evaluator_runs", "pred_table", "predict_finalise", "predict_combine", "rph",
+           "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -55,6 +56,7 @@ EXPORTS = [
     "pht_gibbs_run_chains", "pht_rccl_unique_id", "pht_ctx_rccl_prepare", "pht_ctx_attach_rccl", "pht_ctx_rccl_allreduce",
     "pht_loglik_bytes", "pht_loglik_build", "pht_theta_to_S", "pht_ctx_loglik", "pht_ctx_loglik_reset",
     "pht_ctx_loglik_state", "pht_ctx_loglik_unif", "pht_ctx_loglik_unif_K",
+    "pht_pred_words", "pht_pred_table_words", "pht_pred_build", "pht_ctx_predict",
 ]
 
 
@@ -142,6 +144,11 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_loglik_state.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
     L.pht_ctx_loglik_unif.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _lp, C.c_void_p, C.c_int, _ip]
     L.pht_ctx_loglik_unif_K.argtypes = [C.c_void_p, C.c_double]
+    L.pht_pred_table_words.argtypes = [C.c_int]
+    L.pht_pred_build.argtypes = [C.c_int, _dp, _dp, _dp, C.c_int]
+    L.pht_ctx_predict.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_longlong, C.c_uint32, C.c_uint32,
+                                  C.c_uint32, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _lp, _lp, _dp, _dp,
+                                  C.c_void_p, C.c_void_p, _ip]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -431,6 +438,57 @@ class Sweeper:
             r["evaluator"] = np.full(hi - lo, "unif" if unif else "spectral")
             parts.append(r)
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+    def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
+                horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
+        """pht_ctx_predict: ``nrep`` replicated absorption times of PH(e_1, S)
+        for each draw (S, s), simulated on the GPU (include/pht_predict.h),
+        and their exact reductions.  Needs no observations on the context.
+
+        Replicate r of draw d owns the Philox stream (key; rep0 + r;
+        draw0 + d), so its value does not depend on nrep, batch or the launch.
+        ``edges``: strictly increasing finite values (at most 1024) for the
+        histogram; ``horizon``: paths are stopped there and recorded as
+        y = horizon (``nsurv``); ``max_jumps`` (default and at most 2^20): a
+        longer path is a bad replicate, as is a recorded y >= 2^20.
+
+        Returns per draw ``mean``, ``var`` (unbiased), ``ymin``, ``ymax``,
+        ``ndone``, ``nbad``, ``nsurv``, ``njump``; ``counts`` [draws, ne + 1]
+        (bin = the number of edges <= y) and ``ecdf`` [draws, ne] (the share
+        of recorded replicates below each edge); ``bad_draw`` / ``flags`` (a
+        flagged draw is skipped: PRED_F_* and LL_F_*); the raw ``words``
+        [draws, 8] int64 ``[Hy, Fy, Hq, Fq, ndone, nbad, nsurv, njump]`` and
+        ``edges``; with ``pointwise`` ``y`` [draws, nrep] (NaN: bad) and
+        ``jumps``.  words and counts are exact integer sums: replicate ranges
+        and ranks add (``predict_combine``, or the int64 reduce ``gibbs`` is
+        given, then ``predict_finalise``), ymin / ymax combine by min / max.
+        At most 2^22 replicates per call: split longer runs by ``rep0``."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd = S_all.shape[0]
+        if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
+            raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
+        edges = np.zeros(0) if edges is None else np.ascontiguousarray(edges, np.float64).reshape(-1)
+        ne, nrep = len(edges), int(nrep)
+        if not 1 <= nrep <= PRED_MAX_REP:
+            raise ValueError(f"nrep = {nrep} outside 1..2^22 (split a longer run by rep0)")
+        words = np.zeros(PRED_WORDS * nd, np.int64)
+        counts = np.zeros(nd * (ne + 1), np.int64)
+        ymin, ymax = np.zeros(nd), np.zeros(nd)
+        flags = np.zeros(nd, np.int32)
+        y = np.full((nd, max(nrep, 0)), np.nan) if pointwise else None
+        nj = np.zeros((nd, max(nrep, 0)), np.int32) if pointwise else None
+        if self.L.pht_ctx_predict(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), nrep, int(rep0), int(draw0),
+                                  int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF, float(horizon),
+                                  PRED_MAX_JUMPS if max_jumps is None else int(max_jumps), ne,
+                                  edges if ne else np.zeros(1), int(batch), words, counts, ymin, ymax,
+                                  y.ctypes.data if pointwise else None, nj.ctypes.data if pointwise else None,
+                                  flags) != 0:
+            raise _err(self.L)
+        out = predict_finalise(words.reshape(nd, PRED_WORDS), counts.reshape(nd, ne + 1), ymin, ymax, flags, edges)
+        if pointwise:
+            out["y"], out["jumps"] = y, nj
+        return out
 
     def waic_reset(self) -> None:
         """Forget the per-observation WAIC state (pht_ctx_loglik_reset)."""
@@ -807,3 +865,213 @@ def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int =
     finally:
         sw.close()
     return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))
+
+
+# ------------------------------------------------- posterior-predictive checks
+# include/pht_predict.h, phasetype_amd/csrc/pht_predict.hip (no reference
+# counterpart): replicated absorption times of PH(e_1, S_d) for posterior
+# draws, reduced exactly on the GPU; everything below the kernel call is numpy.
+PRED_WORDS = 8  # int64 words per draw: [Hy, Fy, Hq, Fq, ndone, nbad, nsurv, njump]
+PRED_MAX_REP = 1 << 22  # replicates per draw and call
+PRED_MAX_EDGES = 1024
+PRED_MAX_JUMPS = 1 << 20
+PRED_F_RATE, PRED_F_ABSORB = 16, 32  # flag words next to LL_F_NONFINITE, LL_F_MU (pht_predict.h)
+
+
+def pred_table(S, s):
+    """One draw's table (pht_pred_build; host only): (flag, scale [n],
+    cum [n, n]), the per-row running sums of the jump probabilities over the
+    candidates k != j in increasing k, the exit last, +inf from the last
+    candidate of positive probability on.  A flagged draw's table is zero."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    words = L.pht_pred_table_words(n)
+    if words < 0 or S.shape != (n, n):
+        raise ValueError(f"S must be square with 1 <= n <= 32, got {S.shape}")
+    tab = np.zeros(words)
+    flag = L.pht_pred_build(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                            np.ascontiguousarray(s, np.float64).reshape(-1), tab, words)
+    if flag < 0:
+        raise _err(L)
+    return flag, tab[:n].copy(), tab[n:].reshape(n, n).copy()
+
+
+def predict_finalise(words, counts, ymin, ymax, flags, edges) -> dict:
+    """``Sweeper.predict``'s dict from the (summed) integer words and counts,
+    the (min / max combined) extremes, the flag words and the edges."""
+    words = np.asarray(words, np.int64).reshape(-1, PRED_WORDS)
+    nd = words.shape[0]
+    edges = np.asarray(edges, np.float64).reshape(-1)
+    counts = np.asarray(counts, np.int64).reshape(nd, len(edges) + 1)
+    flags = np.asarray(flags, np.int32).reshape(nd)
+    ndone = words[:, 4].astype(np.float64)
+    sy = words[:, 0].astype(np.float64) + words[:, 1].astype(np.float64) * 2.0 ** -32
+    sq = words[:, 2].astype(np.float64) + words[:, 3].astype(np.float64) * 2.0 ** -32
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(ndone > 0, sy / ndone, np.nan)
+        var = np.where(ndone > 1, (sq - sy * sy / ndone) / (ndone - 1.0), np.nan)
+        ecdf = np.where(ndone[:, None] > 0, np.cumsum(counts[:, :-1], axis=1) / ndone[:, None], np.nan)
+    some = ndone > 0
+    return dict(mean=mean, var=var, ymin=np.where(some, np.asarray(ymin, np.float64), np.nan),
+                ymax=np.where(some, np.asarray(ymax, np.float64), np.nan), ndone=words[:, 4].copy(),
+                nbad=words[:, 5].copy(), nsurv=words[:, 6].copy(), njump=words[:, 7].copy(), counts=counts,
+                ecdf=ecdf, words=words, bad_draw=flags != 0, flags=flags, edges=edges)
+
+
+def predict_combine(a: dict, b: dict) -> dict:
+    """Two ``predict`` results of the same draws and edges over disjoint
+    replicate ranges, as one: words and counts add, ymin / ymax combine by
+    min / max, pointwise values are joined in the order (a, b)."""
+    if a["words"].shape != b["words"].shape or not np.array_equal(a["edges"], b["edges"]):
+        raise ValueError("the two results must cover the same draws with the same edges")
+    if not np.array_equal(a["flags"], b["flags"]):
+        raise ValueError("the two results flag different draws")
+    out = predict_finalise(a["words"] + b["words"], a["counts"] + b["counts"],
+                           np.fmin(a["ymin"], b["ymin"]), np.fmax(a["ymax"], b["ymax"]), a["flags"], a["edges"])
+    if "y" in a and "y" in b:
+        out["y"] = np.concatenate([a["y"], b["y"]], axis=1)
+        out["jumps"] = np.concatenate([a["jumps"], b["jumps"]], axis=1)
+    return out
+
+
+def _predict_chunks(sw, S_list, s_list, nrep, **kw):
+    """sw.predict over nrep replicates in calls of at most 2^22, by rep0"""
+    out, rep0 = None, int(kw.pop("rep0", 0))
+    nrep = int(nrep)
+    if nrep < 1:
+        raise ValueError("nrep must be at least 1")
+    for lo in range(0, nrep, PRED_MAX_REP):
+        r = sw.predict(S_list, s_list, min(PRED_MAX_REP, nrep - lo), rep0=rep0 + lo, **kw)
+        out = r if out is None else predict_combine(out, r)
+    return out
+
+
+def rph(S, s, N: int, key=(1, 2), device: int = 0) -> np.ndarray:
+    """N variates of PH(e_1, S) (absorption times of the chain started in
+    state 1), simulated on the GPU: variate i is replicate i of draw 0 under
+    ``key``, whatever N is.  NaN where a path exceeded 2^20 jumps or 2^20."""
+    S = np.asarray(S, np.float64)
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        r = _predict_chunks(sw, [S], [s], N, key=key, pointwise=True)
+        if r["bad_draw"][0]:
+            raise ValueError(f"not a phase-type generator with certain absorption from state 1 (flag {r['flags'][0]})")
+        return r["y"][0]
+    finally:
+        sw.close()
+
+
+def posterior_predictive(res, TT_or_T, nrep: int, edges=None, C_=None, n=None, burn: int = 0, thin: int = 1,
+                         key=(1, 2), horizon: float = np.inf, device: int = 0, batch: int = 64,
+                         collation: str = "C") -> dict:
+    """``Sweeper.predict`` over the rows ``burn::thin`` of a chain (``res`` and
+    ``TT_or_T`` as in ``log_lik``): ``nrep`` replicated absorption times per
+    row, their moments, extremes and histogram on ``edges``.  Row k of the
+    selection is draw number k of the streams."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    try:
+        return _predict_chunks(sw, S_list, s_list, nrep, key=key, edges=edges, horizon=horizon, batch=batch)
+    finally:
+        sw.close()
+
+
+def quantiles_from_counts(counts, edges, ymin, ymax, q) -> np.ndarray:
+    """Quantiles [draws, len(q)] of histogrammed values: ``counts``
+    [draws, ne + 1] over ``edges`` (bin = the number of edges <= y), the
+    outer bins closed by ymin / ymax; linear within the bin that holds the
+    rank q * total (the histogram's resolution: exact at an edge)."""
+    counts = np.atleast_2d(np.asarray(counts, np.float64))
+    edges = np.asarray(edges, np.float64).reshape(-1)
+    q = np.atleast_1d(np.asarray(q, np.float64))
+    nd = counts.shape[0]
+    lo = np.concatenate([np.asarray(ymin, np.float64).reshape(nd, 1), np.broadcast_to(edges, (nd, len(edges)))], axis=1)
+    hi = np.concatenate([np.broadcast_to(edges, (nd, len(edges))), np.asarray(ymax, np.float64).reshape(nd, 1)], axis=1)
+    lo, hi = np.minimum(lo, hi), np.maximum(lo, hi)  # (an extreme inside a neighbouring bin's range)
+    cum = np.cumsum(counts, axis=1)
+    out = np.full((nd, len(q)), np.nan)
+    for d in range(nd):
+        tot = cum[d, -1]
+        if not tot > 0:
+            continue
+        for i, qq in enumerate(q):
+            rank = qq * tot
+            b = min(int(np.searchsorted(cum[d], rank, "left")), counts.shape[1] - 1)
+            below = cum[d, b - 1] if b > 0 else 0.0
+            frac = (rank - below) / counts[d, b] if counts[d, b] > 0 else 0.0
+            out[d, i] = lo[d, b] + frac * (hi[d, b] - lo[d, b])
+    return out
+
+
+def _ppc_data(x, censored, horizon):
+    """(x as recorded, horizon or inf): exact data, or administratively
+    censored at ``horizon`` (every censored observation equals it)"""
+    x = np.asarray(x, np.float64).reshape(-1)
+    if len(x) < 2:
+        raise ValueError("need at least two observations")
+    cen = np.zeros(len(x), bool) if censored is None else np.asarray(censored).reshape(-1) != 0
+    if len(cen) != len(x):
+        raise ValueError("censored must have the data's length")
+    if cen.any():
+        if horizon is None:
+            raise ValueError("ppc compares exact data; censored observations need `horizon` (administrative "
+                             "censoring: every censored observation equals it)")
+        if not np.all(x[cen] == float(horizon)) or np.any(x[~cen] > float(horizon)):
+            raise ValueError("with `horizon`, every censored observation must equal it and no exact one exceed it")
+    return x, (np.inf if horizon is None else float(horizon))
+
+
+def ppc_from_predict(pred: dict, x, quantiles=(.05, .25, .5, .75, .95)) -> dict:
+    """The numpy finalisation of ``ppc``: ``pred`` a ``predict`` result whose
+    edges are the sorted distinct values of the data ``x`` (as recorded).
+
+    Per usable draw (not flagged, some replicate recorded) the test
+    quantities T(y_rep) — mean, sd, min, max from the exact words, the
+    quantiles from the histogram (``quantiles_from_counts``) — against T(x);
+    ``p[name]`` = mean(T(y_rep) >= T(x)) over those draws.  ``band``: the
+    2.5 / 50 / 97.5 % of ``ecdf`` over the draws at each edge, ``ecdf_x`` the
+    data's share below each edge (the same convention)."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    use = (~np.asarray(pred["bad_draw"], bool)) & (np.asarray(pred["ndone"]) > 1)
+    edges = np.asarray(pred["edges"], np.float64)
+    qs = tuple(float(v) for v in quantiles)
+    qrep = quantiles_from_counts(pred["counts"], edges, pred["ymin"], pred["ymax"], qs)
+    T_rep = dict(mean=pred["mean"], sd=np.sqrt(pred["var"]), min=pred["ymin"], max=pred["ymax"])
+    T_x = dict(mean=float(np.mean(x)), sd=float(np.std(x, ddof=1)), min=float(np.min(x)), max=float(np.max(x)))
+    for i, v in enumerate(qs):
+        T_rep[f"q{v:g}"] = qrep[:, i]
+        T_x[f"q{v:g}"] = float(np.quantile(x, v))
+    T_rep = {k: np.asarray(v, np.float64) for k, v in T_rep.items()}
+    p = {k: (float(np.mean(T_rep[k][use] >= T_x[k])) if use.any() else np.nan) for k in T_rep}
+    out = dict(p=p, T_x=T_x, T_rep=T_rep, n_draws_used=int(use.sum()), edges=edges,
+               ecdf_x=np.array([np.mean(x < e) for e in edges]))
+    out["band"] = (np.quantile(pred["ecdf"][use], [.025, .5, .975], axis=0) if use.any()
+                   else np.full((3, len(edges)), np.nan))
+    return out
+
+
+def ppc(res, x, TT_or_T=None, nrep=None, censored=None, horizon=None, quantiles=(.05, .25, .5, .75, .95), C_=None,
+        n=None, burn: int = 0, thin: int = 1, key=(1, 2), device: int = 0, batch: int = 64,
+        collation: str = "C") -> dict:
+    """Posterior predictive check of a chain against data ``x``: for every row
+    (``burn::thin``) ``nrep`` (default len(x)) replicates on the GPU
+    (``posterior_predictive``), histogrammed on the data's sorted distinct
+    values (thinned evenly to 1024 edges where there are more), then
+    ``ppc_from_predict``.  Exact data only; with ``censored``, ``horizon``
+    must be given and every censored observation equal it (administrative
+    censoring): data and replicates are then both compared as recorded at the
+    horizon.  Returns ``ppc_from_predict``'s dict plus ``predict``."""
+    x, hz = _ppc_data(x, censored, horizon)
+    edges = np.unique(x)
+    if len(edges) > PRED_MAX_EDGES:
+        edges = edges[np.unique(np.round(np.linspace(0, len(edges) - 1, PRED_MAX_EDGES)).astype(np.int64))]
+    pred = posterior_predictive(res, TT_or_T, len(x) if nrep is None else int(nrep), edges=edges, C_=C_, n=n,
+                                burn=burn, thin=thin, key=key, horizon=hz, device=device, batch=batch,
+                                collation=collation)
+    out = ppc_from_predict(pred, x, quantiles)
+    out["predict"] = pred
+    return out

@@ -12,6 +12,7 @@
  *   host_gibbs.cpp     Gibbs bookkeeping and loop, pht_gibbs_run, pht_theta_to_S
  *   host_resident.cpp  pht_gibbs_run_resident
  *   host_loglik.cpp    log-likelihood blocks, pht_ctx_loglik* and pht_ctx_loglik_unif*
+ *   host_predict.cpp   posterior-predictive replicates, pht_pred_* and pht_ctx_predict
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -217,6 +218,14 @@ struct pht_ctx {
    * [draw][k][2]; its own buffer, never the sampler's obs.d_utab */
   DevBuf<double> d_lluin, d_llutab;
   size_t lluin_cap = 0, llutab_cap = 0;
+  /* pht_ctx_predict (allocated on first use; its own buffers, never the
+   * sampler's): a call's tables + edges, flags, result words ([nd][8] sums,
+   * [nd] ymin, [nd] ymax, [nd][ne + 1] counts) and one batch's pointwise
+   * values and jump counts */
+  DevBuf<double> d_predin, d_predy;
+  DevBuf<int> d_predflag, d_prednj;
+  DevBuf<unsigned long long> d_predout;
+  size_t predin_cap = 0, predy_cap = 0, predflag_cap = 0, prednj_cap = 0, predout_cap = 0;
 };
 
 namespace pht {
