@@ -205,6 +205,36 @@ int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s
                         double *pointwise, int accumulate, int *flags_out);
 int pht_ctx_loglik_unif_K(pht_ctx *c, double mu);
 
+/* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
+ * the whole definition): per observation, from l[d, i] of every usable draw
+ * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail
+ * and lppd_i.  The pointwise matrix stays on the device: ndraws * count * 8
+ * bytes (plus a transposed chunk of at most 256 MB and 28 bytes per
+ * observation), which must fit the device's free memory with 512 MB to spare;
+ * there is no chunking over observations: thin the chain instead.  Limits:
+ * 1 <= ndraws <= 16384; smoothing needs at least 25 usable draws.
+ *
+ * pht_ctx_loo_begin: allocates the matrix for ndraws rows and marks every row
+ *   unusable; fails (message in pht_last_error) when it does not fit, without
+ *   observations, or with ndraws out of range.  A new pht_ctx_set_obs drops it.
+ * pht_ctx_loo_fill / pht_ctx_loo_fill_unif: rows [row0, row0 + nd) from nd
+ *   draws by the spectral / uniformisation evaluator, arguments and totals as
+ *   in pht_ctx_loglik / pht_ctx_loglik_unif (so the trace comes with it); no
+ *   host copy of the rows; the WAIC state is not touched.  A row is usable
+ *   when its draw's flag word is 0.  Any row order, any split, any batch.
+ * pht_ctx_loo: count values each, in the caller's observation order; flags:
+ *   1 an l of a usable draw is NaN (outputs NaN), 2 fewer than 25 usable
+ *   draws, 4 constant tail, 8 no finite fit (2, 4, 8: khat = +inf, elpd by
+ *   plain importance sampling).  ndraws_used: NULL or the usable rows.
+ *   pht_ctx_last_kernel_ms then gives the device time of its kernels.
+ * pht_ctx_loo_end frees the matrix. */
+int pht_ctx_loo_begin(pht_ctx *c, int ndraws);
+int pht_ctx_loo_fill(pht_ctx *c, int row0, int nd, const unsigned char *blocks, int batch, long long *totals);
+int pht_ctx_loo_fill_unif(pht_ctx *c, int row0, int nd, const double *S, const double *s, int batch,
+                          long long *totals, int *flags_out);
+int pht_ctx_loo(pht_ctx *c, double *elpd, double *khat, double *lppd, int *flags, int *ndraws_used);
+int pht_ctx_loo_end(pht_ctx *c);
+
 /* Posterior-predictive replicates (include/pht_predict.h): for each draw
  * (S, s), nrep absorption times of PH(e_1, S) simulated forward on the GPU, and
  * their exact integer reductions.  Limits: pi = e_1; a recorded time below

@@ -27,7 +27,8 @@ from . import build as _build
 __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains", "PhaseTypeError", "METHODS",
            "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S",
            "EVALUATORS", "evaluator_runs", "pred_table", "predict_finalise", "predict_combine", "rph",
-           "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts"]
+           "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts", "loo", "loo_from_psis",
+           "loo_compare", "PSIS_MAX_DRAWS"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -57,6 +58,7 @@ EXPORTS = [
     "pht_loglik_bytes", "pht_loglik_build", "pht_theta_to_S", "pht_ctx_loglik", "pht_ctx_loglik_reset",
     "pht_ctx_loglik_state", "pht_ctx_loglik_unif", "pht_ctx_loglik_unif_K",
     "pht_pred_words", "pht_pred_table_words", "pht_pred_build", "pht_ctx_predict",
+    "pht_ctx_loo_begin", "pht_ctx_loo_fill", "pht_ctx_loo_fill_unif", "pht_ctx_loo", "pht_ctx_loo_end",
 ]
 
 
@@ -149,6 +151,11 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_predict.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_longlong, C.c_uint32, C.c_uint32,
                                   C.c_uint32, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _lp, _lp, _dp, _dp,
                                   C.c_void_p, C.c_void_p, _ip]
+    L.pht_ctx_loo_begin.argtypes = [C.c_void_p, C.c_int]
+    L.pht_ctx_loo_fill.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, _lp]
+    L.pht_ctx_loo_fill_unif.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _lp, _ip]
+    L.pht_ctx_loo.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, C.POINTER(C.c_int)]
+    L.pht_ctx_loo_end.argtypes = [C.c_void_p]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -488,6 +495,100 @@ class Sweeper:
         out = predict_finalise(words.reshape(nd, PRED_WORDS), counts.reshape(nd, ne + 1), ymin, ymax, flags, edges)
         if pointwise:
             out["y"], out["jumps"] = y, nj
+        return out
+
+    def loo_begin(self, ndraws: int) -> None:
+        """pht_ctx_loo_begin: the device matrix [ndraws, observations] of a
+        PSIS-LOO, every row unusable until filled (loo_fill); raises when it
+        does not fit the device's free memory (thin the chain)."""
+        if self.L.pht_ctx_loo_begin(self.ctx, int(ndraws)) != 0:
+            raise _err(self.L)
+
+    def loo_fill(self, row0: int, S_list=None, s_list=None, blocks=None, batch: int = 64, unif: bool = False):
+        """Rows [row0, row0 + draws) of the matrix from draws (S, s) by
+        uniformisation (``unif``) or from their spectral ``blocks``
+        (pht_ctx_loo_fill_unif / pht_ctx_loo_fill).  Returns int64
+        [draws, 4] totals ``[H, F, nbad, nobs]`` and the bool ``bad_draw``."""
+        if unif:
+            S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+            s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+            nd = S_all.shape[0]
+            if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
+                raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
+            tot, flags = np.zeros(4 * nd, np.int64), np.zeros(nd, np.int32)
+            if self.L.pht_ctx_loo_fill_unif(self.ctx, int(row0), nd, S_all.reshape(-1), s_all.reshape(-1), int(batch),
+                                            tot, flags) != 0:
+                raise _err(self.L)
+            return tot.reshape(nd, 4), flags != 0
+        blocks = np.ascontiguousarray(blocks, np.uint8)
+        nb = self.L.pht_loglik_bytes(self.n)
+        if blocks.ndim != 2 or blocks.shape[1] != nb or blocks.shape[0] < 1:
+            raise ValueError(f"blocks must be [draws >= 1, {nb}] bytes for n = {self.n}")
+        nd = blocks.shape[0]
+        tot = np.zeros(4 * nd, np.int64)
+        if self.L.pht_ctx_loo_fill(self.ctx, int(row0), nd, blocks.ctypes.data, int(batch), tot) != 0:
+            raise _err(self.L)
+        return tot.reshape(nd, 4), blocks[:, :8].copy().view(np.uint64).reshape(nd) != 0
+
+    def loo_result(self) -> dict:
+        """pht_ctx_loo over the rows filled so far: dict(elpd_i, khat,
+        lppd_i, p_loo_i, flags, n_draws_used), the caller's observation order."""
+        elpd, khat, lppd = np.zeros(self.count), np.zeros(self.count), np.zeros(self.count)
+        flags = np.zeros(self.count, np.int32)
+        used = C.c_int(0)
+        if self.L.pht_ctx_loo(self.ctx, elpd, khat, lppd, flags, C.byref(used)) != 0:
+            raise _err(self.L)
+        return dict(elpd_i=elpd, khat=khat, lppd_i=lppd, p_loo_i=lppd - elpd, flags=flags, n_draws_used=used.value)
+
+    def loo_end(self) -> None:
+        """Free the PSIS-LOO matrix (pht_ctx_loo_end)."""
+        if self.L.pht_ctx_loo_end(self.ctx) != 0:
+            raise _err(self.L)
+
+    def psis_loo(self, S_list, s_list, batch: int = 64, evaluator: str = "spectral", blocks=None) -> dict:
+        """PSIS-LOO cross-validation of this shard's observations over the
+        draws (S, s) (include/pht_psis.h; Vehtari, Gelman, Gabry 2017): the
+        pointwise log-likelihood matrix is filled and kept on the device, then
+        one wavefront per observation selects the tail of the importance
+        ratios, fits the generalised Pareto and smooths.
+
+        Returns per observation ``elpd_i``, ``khat`` (the Pareto shape; +inf
+        where nothing was smoothed), ``lppd_i``, ``p_loo_i = lppd_i - elpd_i``
+        and ``flags`` (1: an l of a usable draw is NaN, outputs NaN; 2: fewer
+        than 25 usable draws; 4: constant tail; 8: no finite fit); per draw
+        ``bad_draw``, ``evaluator`` and ``total`` (the log-likelihood trace,
+        as Sweeper.loglik gives it); ``n_draws_used``.  ``evaluator`` and
+        ``blocks`` as in Sweeper.loglik; flagged draws are left out.  At most
+        16384 draws; the matrix (draws x observations x 8 bytes) must fit the
+        device: thin the chain otherwise.  The WAIC state is not touched.
+        Observations are independent: shards and ranks each run their own,
+        and the sums over elpd_i add."""
+        if evaluator not in EVALUATORS:
+            raise ValueError(f"evaluator must be one of {EVALUATORS}, got {evaluator!r}")
+        S_list, s_list = list(S_list), list(s_list)
+        nd = len(S_list)
+        if evaluator != "unif" and blocks is None:
+            blocks = np.stack([loglik_block(S, s) for S, s in zip(S_list, s_list)])
+        if evaluator == "unif":
+            runs = [(0, nd, True)]
+        elif evaluator == "spectral":
+            runs = [(0, nd, False)]
+        else:
+            runs = evaluator_runs(np.ascontiguousarray(blocks[:, :8]).view(np.uint64).reshape(-1))
+        tot, bad = np.zeros((nd, 4), np.int64), np.zeros(nd, bool)
+        which = np.full(nd, "spectral", dtype="<U8")
+        self.loo_begin(nd)
+        try:
+            for lo, hi, unif in runs:
+                if unif:
+                    tot[lo:hi], bad[lo:hi] = self.loo_fill(lo, S_list[lo:hi], s_list[lo:hi], batch=batch, unif=True)
+                    which[lo:hi] = "unif"
+                else:
+                    tot[lo:hi], bad[lo:hi] = self.loo_fill(lo, blocks=blocks[lo:hi], batch=batch)
+            out = self.loo_result()
+        finally:
+            self.loo_end()
+        out.update(bad_draw=bad, evaluator=which, total=loglik_total(tot[:, 0], tot[:, 1], tot[:, 2], bad))
         return out
 
     def waic_reset(self) -> None:
@@ -865,6 +966,54 @@ def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int =
     finally:
         sw.close()
     return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))
+
+
+# ------------------------------------------------------------- PSIS-LOO
+# include/pht_psis.h, phasetype_amd/csrc/pht_psis.hip (no reference
+# counterpart); everything below Sweeper.psis_loo is numpy.
+PSIS_MAX_DRAWS = 16384
+
+
+def loo_from_psis(r: dict) -> dict:
+    """The summary of a Sweeper.psis_loo result (or of several shards'
+    results with their per-observation arrays concatenated)."""
+    elpd_i, p_i, khat = np.asarray(r["elpd_i"]), np.asarray(r["p_loo_i"]), np.asarray(r["khat"])
+    N, S = len(elpd_i), int(r["n_draws_used"])
+    elpd = float(np.sum(elpd_i))
+    thr = min(1.0 - 1.0 / np.log10(S), 0.7) if S > 1 else 0.0
+    return dict(elpd_loo=elpd, p_loo=float(np.sum(p_i)), looic=-2.0 * elpd,
+                se_elpd_loo=float(np.sqrt(N * np.var(elpd_i))), lppd=float(np.sum(r["lppd_i"])),
+                pointwise=(elpd_i, p_i, khat), khat_threshold=float(thr), n_khat_above=int(np.sum(khat > thr)),
+                n_draws_used=S)
+
+
+def loo(res, x, TT_or_T=None, censored=None, C_=None, n=None, burn: int = 0, thin: int = 1, device: int = 0,
+        batch: int = 64, collation: str = "C", evaluator: str = "spectral") -> dict:
+    """PSIS-LOO cross-validation of a chain (rows ``burn::thin``) over data
+    ``x`` / ``censored`` (Sweeper.psis_loo): dict(elpd_loo, p_loo, looic,
+    se_elpd_loo = sqrt(N var(elpd_i)), lppd, pointwise=(elpd_i, p_loo_i,
+    khat), khat_threshold = min(1 - 1 / log10(S), 0.7), n_khat_above,
+    n_draws_used).  An observation with khat above the threshold is one whose
+    leave-one-out density these draws cannot estimate; WAIC is off there too,
+    silently.  At most 16384 draws after thinning, and draws x observations x
+    8 bytes must fit the device: thin further otherwise."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        return loo_from_psis(sw.psis_loo(S_list, s_list, batch=batch, evaluator=evaluator))
+    finally:
+        sw.close()
+
+
+def loo_compare(a: dict, b: dict) -> dict:
+    """Two ``loo`` results on the same data: dict(elpd_diff = elpd_a - elpd_b,
+    se_diff = sqrt(N var(elpd_i^a - elpd_i^b))).  numpy only."""
+    ea, eb = np.asarray(a["pointwise"][0], np.float64), np.asarray(b["pointwise"][0], np.float64)
+    if ea.shape != eb.shape:
+        raise ValueError(f"the two results cover {ea.shape} and {eb.shape} observations: not the same data")
+    d = ea - eb
+    return dict(elpd_diff=float(np.sum(d)), se_diff=float(np.sqrt(len(d) * np.var(d))))
 
 
 # ------------------------------------------------- posterior-predictive checks

@@ -13,6 +13,7 @@
  *   host_resident.cpp  pht_gibbs_run_resident
  *   host_loglik.cpp    log-likelihood blocks, pht_ctx_loglik* and pht_ctx_loglik_unif*
  *   host_predict.cpp   posterior-predictive replicates, pht_pred_* and pht_ctx_predict
+ *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -158,6 +159,17 @@ struct pht_ctx {
     size_t llpw_cap = 0;
     DevBuf<double> d_waic;
     DevBuf<long long> d_wcnt;
+    /* pht_ctx_loo_*: the pointwise matrix [ndraws][count] in the device
+     * (sorted) order, which rows a fill made usable, one transposed chunk
+     * [chunk_obs][ndraws], the results [elpd khat lppd][count] and the flag
+     * words; ndraws = 0: no pht_ctx_loo_begin yet */
+    struct Loo {
+      DevBuf<double> d_mat, d_chunk, d_out;
+      DevBuf<int> d_flags, d_rows;
+      int ndraws = 0;
+      long chunk_obs = 0;
+      std::vector<unsigned char> usable;
+    } loo;
   } obs;
   DevBuf<unsigned char> d_params;
   DevBuf<unsigned long long> d_stats;

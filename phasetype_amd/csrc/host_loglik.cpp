@@ -9,6 +9,8 @@
  * whose coefficients are not finite is flagged and never evaluated.
  * Uniformisation (include/pht_loglik_unif.h, pht_loglik_unif.hip;
  * pht_ctx_loglik_unif): any finite generator, straight from (S, s), no LAPACK.
+ * pht_ctx_loo_fill / pht_ctx_loo_fill_unif are the same two calls with their
+ * pointwise rows kept on the device for PSIS-LOO (host_psis.cpp).
  */
 #include <math.h>
 #include <string.h>
@@ -155,10 +157,12 @@ struct LoglikOut {
  * either kind with `accumulate` continue one state), the batches in draw
  * order, the pointwise rows back in the caller's observation order, the
  * device time of the call.  launch(d0, nb, out) enqueues draws [d0, d0 + nb)
- * on the context's stream. */
+ * on the context's stream.  dev_rows (pht_ctx_loo_fill*): the kernels write
+ * the pointwise rows of draw d at dev_rows + d * count instead, in the device
+ * order, and nothing is staged or copied. */
 template <class Launch>
 static int loglik_batches(pht_ctx *c, int ndraws, int batch, long long *totals, double *pointwise, int accumulate,
-                          Launch launch) {
+                          double *dev_rows, Launch launch) {
   hipStream_t st = c->stream.get();
   const long count = c->count;
   if (!c->ll_grid_cap) {
@@ -180,7 +184,7 @@ static int loglik_batches(pht_ctx *c, int ndraws, int batch, long long *totals, 
     const int nb = std::min(batch, ndraws - d0);
     LoglikOut o{};
     o.totals = c->d_lltot.get() + (size_t)d0 * PHT_LL_TOT;
-    o.pw = pointwise ? c->obs.d_llpw.get() : nullptr;
+    o.pw = dev_rows ? dev_rows + (size_t)d0 * (size_t)count : (pointwise ? c->obs.d_llpw.get() : nullptr);
     o.acc = accumulate ? 1 : 0;
     if (accumulate) {
       o.w_ref = c->obs.d_waic.get();
@@ -210,11 +214,11 @@ static int loglik_batches(pht_ctx *c, int ndraws, int batch, long long *totals, 
   return 0;
 }
 
-extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
-                              double *pointwise, int accumulate) {
-  if (loglik_need_obs(c, "pht_ctx_loglik")) return -1;
+/* the spectral evaluator's call (dev_rows: loglik_batches) */
+static int loglik_spectral(pht_ctx *c, const char *who, int ndraws, const unsigned char *blocks, int batch,
+                           long long *totals, double *pointwise, int accumulate, double *dev_rows) {
   if (ndraws < 1 || !blocks || !totals || batch < 1 || batch > kLoglikBatch) {
-    set_err("pht_ctx_loglik: need ndraws >= 1, blocks, totals and 1 <= batch <= %d", kLoglikBatch);
+    set_err("%s: need ndraws >= 1, blocks, totals and 1 <= batch <= %d", who, kLoglikBatch);
     return -1;
   }
   HIPCHK(hipSetDevice(c->device));
@@ -223,7 +227,8 @@ extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *block
   const int n = c->n, words = pht_ll_words(n);
   HIPCHK(ensure(c->d_llblk, c->llblk_cap, (size_t)ndraws * words));
   HIPCHK(hipMemcpyAsync(c->d_llblk.get(), blocks, 8 * (size_t)ndraws * words, hipMemcpyHostToDevice, st));
-  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, [&](int d0, int nb, const LoglikOut &o) {
+  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, dev_rows,
+                        [&](int d0, int nb, const LoglikOut &o) {
     LoglikArgs a{};
     a.n = n;
     a.nd = nb;
@@ -245,6 +250,12 @@ extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *block
   });
 }
 
+extern "C" int pht_ctx_loglik(pht_ctx *c, int ndraws, const unsigned char *blocks, int batch, long long *totals,
+                              double *pointwise, int accumulate) {
+  if (loglik_need_obs(c, "pht_ctx_loglik")) return -1;
+  return loglik_spectral(c, "pht_ctx_loglik", ndraws, blocks, batch, totals, pointwise, accumulate, nullptr);
+}
+
 extern "C" int pht_ctx_loglik_unif_K(pht_ctx *c, double mu) {
   if (loglik_need_obs(c, "pht_ctx_loglik_unif_K")) return -1;
   if (!(mu > 0.0) || !std::isfinite(mu)) {
@@ -254,11 +265,11 @@ extern "C" int pht_ctx_loglik_unif_K(pht_ctx *c, double mu) {
   return pht_llu_K(mu, c->ymax);
 }
 
-extern "C" int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s, int batch,
-                                   long long *totals, double *pointwise, int accumulate, int *flags_out) {
-  if (loglik_need_obs(c, "pht_ctx_loglik_unif")) return -1;
+/* the uniformisation evaluator's call (dev_rows: loglik_batches) */
+static int loglik_unif(pht_ctx *c, const char *who, int ndraws, const double *S, const double *s, int batch,
+                       long long *totals, double *pointwise, int accumulate, int *flags_out, double *dev_rows) {
   if (ndraws < 1 || !S || !s || !totals || batch < 1 || batch > kLoglikBatch) {
-    set_err("pht_ctx_loglik_unif: need ndraws >= 1, S, s, totals and 1 <= batch <= %d", kLoglikBatch);
+    set_err("%s: need ndraws >= 1, S, s, totals and 1 <= batch <= %d", who, kLoglikBatch);
     return -1;
   }
   HIPCHK(hipSetDevice(c->device));
@@ -284,7 +295,8 @@ extern "C" int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, cons
   HIPCHK(hipMemcpyAsync(dS, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ds, s, sizeof(double) * ns, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dmeta, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice, st));
-  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, [&](int d0, int nb, const LoglikOut &o) {
+  return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, dev_rows,
+                        [&](int d0, int nb, const LoglikOut &o) {
     int Kmax = 0;
     for (int d = d0; d < d0 + nb; d++) Kmax = std::max(Kmax, (int)meta[(size_t)d * PHT_LLU_META + PHT_LLU_M_K]);
     LlunifTableArgs t{};
@@ -318,6 +330,60 @@ extern "C" int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, cons
     HIPCHK(pht_launch_llunif(&a, std::max(1, c->ll_grid_cap / 2), st));
     return 0;
   });
+}
+
+extern "C" int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s, int batch,
+                                   long long *totals, double *pointwise, int accumulate, int *flags_out) {
+  if (loglik_need_obs(c, "pht_ctx_loglik_unif")) return -1;
+  return loglik_unif(c, "pht_ctx_loglik_unif", ndraws, S, s, batch, totals, pointwise, accumulate, flags_out,
+                     nullptr);
+}
+
+/* ---- PSIS-LOO fills: the same calls, their pointwise rows kept on the device
+ * in the context's matrix (host_psis.cpp owns it), the WAIC state untouched */
+static int loo_fill_rows(pht_ctx *c, const char *who, int row0, int nd) {
+  if (loglik_need_obs(c, who)) return -1;
+  const auto &L = c->obs.loo;
+  if (L.ndraws < 1 || !L.d_mat) {
+    set_err("%s: no matrix on this context (pht_ctx_loo_begin)", who);
+    return -1;
+  }
+  if (row0 < 0 || nd < 1 || (long long)row0 + nd > L.ndraws) {
+    set_err("%s: rows [%d, %lld) outside the matrix's %d draws", who, row0, (long long)row0 + nd, L.ndraws);
+    return -1;
+  }
+  /* unusable until the fill is through (a failed fill leaves them so) */
+  std::fill(c->obs.loo.usable.begin() + row0, c->obs.loo.usable.begin() + row0 + nd, (unsigned char)0);
+  return 0;
+}
+
+extern "C" int pht_ctx_loo_fill(pht_ctx *c, int row0, int nd, const unsigned char *blocks, int batch,
+                                long long *totals) {
+  if (loo_fill_rows(c, "pht_ctx_loo_fill", row0, nd)) return -1;
+  auto &L = c->obs.loo;
+  double *rows = L.d_mat.get() + (size_t)row0 * (size_t)c->count;
+  if (loglik_spectral(c, "pht_ctx_loo_fill", nd, blocks, batch, totals, nullptr, 0, rows)) return -1;
+  const size_t bytes = 8 * (size_t)pht_ll_words(c->n);
+  for (int d = 0; d < nd; d++) {
+    uint64_t flag;
+    memcpy(&flag, blocks + (size_t)d * bytes + 8 * PHT_LL_FLAG, 8);
+    L.usable[(size_t)row0 + d] = flag == 0;
+  }
+  return 0;
+}
+
+extern "C" int pht_ctx_loo_fill_unif(pht_ctx *c, int row0, int nd, const double *S, const double *s, int batch,
+                                     long long *totals, int *flags_out) {
+  if (loo_fill_rows(c, "pht_ctx_loo_fill_unif", row0, nd)) return -1;
+  auto &L = c->obs.loo;
+  double *rows = L.d_mat.get() + (size_t)row0 * (size_t)c->count;
+  std::vector<int> flags(nd, 0);
+  if (loglik_unif(c, "pht_ctx_loo_fill_unif", nd, S, s, batch, totals, nullptr, 0, flags.data(), rows)) return -1;
+  for (int d = 0; d < nd; d++) {
+    L.usable[(size_t)row0 + d] = flags[d] == 0;
+    if (flags_out) flags_out[d] = flags[d];
+  }
+  return 0;
 }
 
 extern "C" int pht_ctx_loglik_reset(pht_ctx *c) {
