@@ -205,6 +205,47 @@ int pht_ctx_loglik_unif(pht_ctx *c, int ndraws, const double *S, const double *s
                         double *pointwise, int accumulate, int *flags_out);
 int pht_ctx_loglik_unif_K(pht_ctx *c, double mu);
 
+/* Expected sufficient statistics given the observations (the E-step;
+ * include/pht_estep.h is the whole definition): per draw (S, s), summed over
+ * the context's observations, Z_i = E[time in state i | y], N_ij =
+ * E[transitions i -> j | y] and E_i = E[exits from i | y] on [0, y], and A_i =
+ * the expected number of censored observations in state i at y, by the same
+ * uniformisation as pht_ctx_loglik_unif (its limits apply: pi = e_1, the table
+ * cap, bad observations counted in nbad and left out).  No reference
+ * counterpart.  The observations enter through int64 histograms only: per
+ * draw pht_estep_words() = 8192 words [class][k][G, T] (class 0 exact, 1
+ * censored; 2048 rows each), exact integer sums that do not depend on batch,
+ * grid or shard and add across shards and ranks (the caller's reduce, or
+ * pht_ctx_rccl_allreduce) PROVIDED every shard uses the same yscale, a power
+ * of two >= every observation of every shard.  Limit: at most 2^22
+ * observations in all shards together (the context's count, or its
+ * pht_ctx_set_global_count); beyond it the call fails.
+ *
+ * pht_ctx_estep: ndraws draws as in pht_ctx_loglik_unif, `batch` (1..64) per
+ *   launch.  yscale: <= 0 for the default, pht_estep_yscale(largest
+ *   observation of this context).  totals: ndraws * 4 int64 [H, F, nbad, nobs],
+ *   bit for bit pht_ctx_loglik_unif's.  words: NULL, or ndraws * 8192 int64.
+ *   Z (ndraws * n), N (ndraws * n * n, N[i + j n] from i to j, diagonal 0),
+ *   E, A (ndraws * n each): all four, or all NULL for the histograms alone (callers
+ *   that reduce across ranks first, then pht_estep_contract).  A flagged draw
+ *   (flags_out as in pht_ctx_loglik_unif) has zero words and NaN statistics.
+ *   The buffers are the context's own: its chain is not affected.
+ * pht_estep_contract: host only (no GPU), one draw's Z, N, E, A from its
+ *   (summed) words, rows 0..K (K = 2047 for words of pht_ctx_estep); bit for
+ *   bit what the device computes.  Returns the draw's flag word, < 0 on error.
+ * pht_ctx_estep_grid_cap: the most blocks of the histogram kernel (0: the
+ *   default, one a CU); the results do not depend on it.
+ * pht_ctx_estep_ms: device time of the last call, the histograms (with the
+ *   tables) and the contraction. */
+int pht_estep_words(void);
+double pht_estep_yscale(double ymax);
+int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const double *s, int batch, double yscale,
+                  long long *totals, long long *words, double *Z, double *N, double *E, double *A, int *flags_out);
+int pht_estep_contract(int n, const double *S, const double *s, const long long *words, int K, double yscale,
+                       double *Z, double *N, double *E, double *A);
+int pht_ctx_estep_grid_cap(pht_ctx *c, int cap);
+int pht_ctx_estep_ms(pht_ctx *c, float *hist_ms, float *contract_ms);
+
 /* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
  * the whole definition): per observation, from l[d, i] of every usable draw
  * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail

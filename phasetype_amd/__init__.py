@@ -28,7 +28,8 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "log_lik", "waic", "waic_from_state", "ph_curves", "loglik_block", "loglik_total", "theta_to_S",
            "EVALUATORS", "evaluator_runs", "pred_table", "predict_finalise", "predict_combine", "rph",
            "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts", "loo", "loo_from_psis",
-           "loo_compare", "PSIS_MAX_DRAWS"]
+           "loo_compare", "PSIS_MAX_DRAWS", "estep_contract", "expected_stats", "complete_stats",
+           "em_step", "ph_em", "ESTEP_MAX_OBS"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -59,6 +60,8 @@ EXPORTS = [
     "pht_ctx_loglik_state", "pht_ctx_loglik_unif", "pht_ctx_loglik_unif_K",
     "pht_pred_words", "pht_pred_table_words", "pht_pred_build", "pht_ctx_predict",
     "pht_ctx_loo_begin", "pht_ctx_loo_fill", "pht_ctx_loo_fill_unif", "pht_ctx_loo", "pht_ctx_loo_end",
+    "pht_estep_words", "pht_estep_yscale", "pht_ctx_estep", "pht_estep_contract", "pht_ctx_estep_grid_cap",
+    "pht_ctx_estep_ms",
 ]
 
 
@@ -156,6 +159,13 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_loo_fill_unif.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _lp, _ip]
     L.pht_ctx_loo.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, C.POINTER(C.c_int)]
     L.pht_ctx_loo_end.argtypes = [C.c_void_p]
+    L.pht_estep_yscale.restype = C.c_double
+    L.pht_estep_yscale.argtypes = [C.c_double]
+    L.pht_ctx_estep.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, _lp, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, _ip]
+    L.pht_estep_contract.argtypes = [C.c_int, _dp, _dp, _lp, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
+    L.pht_ctx_estep_grid_cap.argtypes = [C.c_void_p, C.c_int]
+    L.pht_ctx_estep_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -221,6 +231,7 @@ class Sweeper:
         if not self.ctx:
             raise _err(self.L)
         self.count = 0
+        self.ymax = 0.0  # the largest observation (estep's default yscale)
         self.flagged_obs = 0  # flagged observation-sweeps of the last gibbs() (pht_ctx_flagged_obs)
 
     def set_obs(self, y, censored=None, obs0: int = 0):
@@ -229,6 +240,7 @@ class Sweeper:
         if self.L.pht_ctx_set_obs(self.ctx, y, cen, len(y), obs0) != 0:
             raise _err(self.L)
         self.count = len(y)
+        self.ymax = float(np.max(y)) if len(y) else 0.0
 
     def sweep(self, S, s, key=(1, 2), sweep: int = 1, zexp: int = 40):
         out = np.zeros(stats_len(self.n), np.int64)
@@ -445,6 +457,56 @@ class Sweeper:
             r["evaluator"] = np.full(hi - lo, "unif" if unif else "spectral")
             parts.append(r)
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+    def estep(self, S_list, s_list, batch: int = 64, yscale=None, contract: bool = True, grid_cap: int = 0):
+        """pht_ctx_estep: the expected sufficient statistics of each draw
+        (S, s) given this shard's observations (include/pht_estep.h), by the
+        uniformisation of ``loglik_unif`` (its limits apply).
+
+        Returns ``Z`` [draws, n] (expected time in each state), ``N`` [draws,
+        n, n] (expected transitions, N[d, i, j] from i to j, diagonal 0),
+        ``E`` [draws, n] (expected exits), all on [0, y] and summed over the
+        shard's good observations, ``A`` [draws, n] (the expected number of
+        censored observations in each state at their censoring time; see
+        ``complete_stats``), all None without ``contract``; ``loglik`` (-inf where an
+        observation was bad, NaN for a flagged draw), ``H, F, nbad, nobs`` (the
+        words of ``loglik_unif``, bit for bit), ``flags``, ``words`` (int64
+        [draws, 2, 2048, 2] = [class, k, (G, T)]) and ``yscale``.
+
+        The words are exact integer sums: shards and ranks that share one
+        ``yscale`` (a power of two >= every observation anywhere; default:
+        the smallest for this shard) add their words, then
+        ``estep_contract(S, s, words, yscale)`` gives the statistics of the
+        whole.  ``grid_cap``: most blocks of the histogram kernel (0: the
+        default); the result does not depend on it.  ``last_estep_ms`` then
+        holds the device time of the histograms and of the contraction."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd, n = S_all.shape[0], self.n
+        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
+            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        ys = float(self.L.pht_estep_yscale(self.ymax)) if yscale is None else float(yscale)
+        nw = self.L.pht_estep_words()
+        tot = np.zeros(4 * nd, np.int64)
+        words = np.zeros((nd, nw), np.int64)
+        flags = np.zeros(nd, np.int32)
+        Z, N, E, A = ((np.zeros((nd, n)), np.zeros((nd, n * n)), np.zeros((nd, n)), np.zeros((nd, n))) if contract
+                      else (None, None, None, None))
+        if self.L.pht_ctx_estep_grid_cap(self.ctx, int(grid_cap)) != 0:
+            raise _err(self.L)
+        ptr = (lambda a: a.ctypes.data) if contract else (lambda a: None)
+        if self.L.pht_ctx_estep(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), int(batch), ys, tot,
+                                words.ctypes.data, ptr(Z), ptr(N), ptr(E), ptr(A), flags) != 0:
+            raise _err(self.L)
+        hm, cm = C.c_float(0), C.c_float(0)
+        self.L.pht_ctx_estep_ms(self.ctx, C.byref(hm), C.byref(cm))
+        self.last_estep_ms = (hm.value, cm.value)
+        tot = tot.reshape(nd, 4)
+        out = dict(Z=Z, N=None if N is None else N.reshape(nd, n, n).transpose(0, 2, 1).copy(), E=E, A=A,
+                   H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(), flags=flags,
+                   words=words.reshape(nd, 2, nw // 4, 2), yscale=ys)
+        out["loglik"] = loglik_total(out["H"], out["F"], out["nbad"], flags != 0)
+        return out
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
                 horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
@@ -966,6 +1028,157 @@ def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int =
     finally:
         sw.close()
     return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))
+
+
+# ------------------------------------------- expected statistics, EM fitting
+# include/pht_estep.h, phasetype_amd/csrc/pht_estep.hip (no reference
+# counterpart): the exact conditional expectations of the statistics the
+# sampler draws, and maximum-likelihood / MAP fitting by EM on top of them.
+ESTEP_MAX_OBS = 1 << 22
+
+
+def estep_contract(S, s, words, yscale):
+    """pht_estep_contract (host only, no GPU): dict(Z [n], N [n, n], E [n],
+    A [n], flag) of one draw from its int64 words (``Sweeper.estep``'s, of one shard
+    or summed over shards that shared ``yscale``); bit for bit what the device
+    computes."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    words = np.ascontiguousarray(words, np.int64).reshape(-1)
+    nw = L.pht_estep_words()
+    if S.shape != (n, n) or not 1 <= n <= 32 or words.shape != (nw,):
+        raise ValueError(f"need S [n, n] with 1 <= n <= 32 and {nw} words")
+    Z, N, E, A = np.zeros(n), np.zeros(n * n), np.zeros(n), np.zeros(n)
+    flag = L.pht_estep_contract(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                                np.ascontiguousarray(s, np.float64), words, nw // 4 - 1, float(yscale), Z, N, E, A)
+    if flag < 0:
+        raise _err(L)
+    return dict(Z=Z, N=N.reshape(n, n, order="F").copy(), E=E, A=A, flag=flag)
+
+
+def complete_stats(S, s, Z, N, E, A):
+    """The statistics of the COMPLETED paths from those on [0, y]: a censored
+    observation's path goes on beyond y until absorption, which is what every
+    sampler here draws for it (as the reference does) and sums into its
+    statistics block.  From state occupancy A at the censoring times the rest
+    of the path spends A (-S)^-1 in each state (-S is a non-singular M-matrix:
+    a non-negative inverse), jumps at rate S_ij and exits at rate s_i from
+    there.  Returns (Z, N, E) with that added; sum(E) is then the number of
+    observations."""
+    S = np.asarray(S, np.float64)
+    after = np.linalg.solve(-S.T, np.asarray(A, np.float64))
+    Zc = np.asarray(Z) + after
+    Nc = np.asarray(N) + after[:, None] * (S - np.diag(np.diag(S)))
+    return Zc, Nc, np.asarray(E) + after * np.asarray(s, np.float64)
+
+
+def expected_stats(S, s, x, censored=None, device: int = 0, complete: bool = False) -> dict:
+    """E[z | y], E[N | y], E[exits | y] of PH(e_1, S) with exit rates s, summed
+    over the observations ``x`` / ``censored``: dict(Z [n], N [n, n], E [n],
+    A [n], loglik, nbad) (Sweeper.estep of one draw).  By default on [0, y]
+    (the likelihood's statistics: sum(Z) = sum(x), exits of exact observations
+    only); ``complete``: of the completed paths (``complete_stats``), the
+    expectation of what a sweep of an exact sampler sums."""
+    S = np.asarray(S, np.float64)
+    sw = _obs_sweeper(x, censored, S.shape[0], device)
+    try:
+        r = sw.estep([S], [s])
+    finally:
+        sw.close()
+    Z, N, E, A = r["Z"][0], r["N"][0], r["E"][0], r["A"][0]
+    if complete:
+        Z, N, E = complete_stats(S, s, Z, N, E, A)
+    return dict(Z=Z, N=N, E=E, A=A, loglik=float(r["loglik"][0]), nbad=int(r["nbad"][0]))
+
+
+def em_step(T, C_, Z, N, E, prior=None) -> np.ndarray:
+    """The M-step: per parameter p over its cells of T (numbers 1..m, 0 = a
+    fixed zero), theta_p = sum Nt / sum C_cell Z_i with Nt = N_ij for a
+    transient cell and E_i for the exit column: the likelihood's C Z, not the
+    Gibbs update's z / C (they coincide at C = 1).  ``prior`` = (nu, zeta):
+    the MAP step (nu - 1 + sum Nt) / (zeta + sum C Z) of the Gamma(nu, zeta)
+    prior, floored at 1e-300."""
+    T = np.asarray(T, np.int64)
+    n = T.shape[0] - 1
+    m = int(T.max())
+    num, den = np.zeros(m), np.zeros(m)
+    for i in range(n):
+        for j in range(n + 1):
+            p = int(T[i, j])
+            if p == 0 or i == j:
+                continue
+            num[p - 1] += E[i] if j == n else N[i, j]
+            den[p - 1] += C_[i, j] * Z[i]
+    if prior is not None:
+        num = num + np.asarray(prior[0], np.float64) - 1.0
+        den = den + np.asarray(prior[1], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        theta = num / den
+    return np.maximum(theta, 1e-300) if prior is not None else theta
+
+
+def ph_em(x, TT_or_T, censored=None, C_=None, start=None, prior=None, iters: int = 200, tol: float = 1e-8,
+          device: int = 0, collation: str = "C", estep=None) -> dict:
+    """Maximum-likelihood (or, with ``prior`` = (nu, zeta) per parameter in
+    phtMCMC2's order, MAP) fit of the structured phase-type model by EM, the
+    E-step on the GPU over all of ``x`` / ``censored`` (Sweeper.estep).
+
+    ``TT_or_T``, ``C_`` as in ``log_lik``; ``start``: the first theta (default:
+    every rate 1 / mean(x)).  Stops after ``iters`` iterations or when the
+    objective (log-likelihood, plus the log-prior for MAP) rises by less than
+    ``tol`` (1 + |objective|).  Returns dict(theta (usable as ``start=`` of
+    phtMCMC2 / Sweeper.gibbs), S, s, loglik (the trace: entry k is the
+    log-likelihood at the theta BEFORE update k), objective, iterations,
+    converged).  A generator that becomes flagged or non-finite, or an
+    observation without density, ends the run with a PhaseTypeError.
+    ``estep``: a callable (S, s) -> dict(Z, N, E, loglik) in place of the GPU
+    (the tests drive the loop with the CPU restatement)."""
+    T, names = _tt_numbers(TT_or_T, collation)
+    n1 = T.shape[0]
+    n, m = n1 - 1, int(T.max())
+    C_ = np.ones((n1, n1)) if C_ is None else np.asarray(C_, np.float64)
+    x = np.asarray(x, np.float64)
+    theta = np.full(m, 1.0 / float(np.mean(x))) if start is None else np.array(start, np.float64).reshape(-1)
+    if theta.shape != (m,):
+        raise ValueError(f"start must hold {m} values")
+    if prior is not None:
+        prior = tuple(np.asarray([p[k] for k in names] if isinstance(p, dict) else p, np.float64) for p in prior)
+    sw = None
+    if estep is None:
+        sw = _obs_sweeper(x, censored, n, device)
+
+        def estep(S, s):
+            r = sw.estep([S], [s])
+            if int(r["flags"][0]) != 0:
+                raise PhaseTypeError(f"ph_em: the generator is not usable (flag {int(r['flags'][0])})")
+            return dict(Z=r["Z"][0], N=r["N"][0], E=r["E"][0], loglik=float(r["loglik"][0]))
+    trace, objective, converged, it = [], [], False, 0
+    try:
+        for it in range(1, int(iters) + 1):
+            if not np.all(np.isfinite(theta)):
+                raise PhaseTypeError(f"ph_em: a non-finite rate at iteration {it}")
+            S, s = theta_to_S(theta, T, C_)
+            r = estep(S, s)
+            ll = float(r["loglik"])
+            if not np.isfinite(ll):
+                raise PhaseTypeError(f"ph_em: log-likelihood {ll} at iteration {it} (a bad observation or an "
+                                     "unusable generator)")
+            obj = ll
+            if prior is not None:
+                obj = ll + float(np.sum((prior[0] - 1.0) * np.log(theta) - prior[1] * theta))
+            trace.append(ll)
+            objective.append(obj)
+            if len(objective) > 1 and abs(obj - objective[-2]) < tol * (1.0 + abs(obj)):
+                converged = True
+                break
+            theta = em_step(T, C_, r["Z"], r["N"], r["E"], prior)
+    finally:
+        if sw is not None:
+            sw.close()
+    S, s = theta_to_S(theta, T, C_)
+    return dict(theta=theta, S=S, s=s, loglik=np.array(trace), objective=np.array(objective), iterations=it,
+                converged=converged, vars=names)
 
 
 # ------------------------------------------------------------- PSIS-LOO

@@ -14,6 +14,7 @@
  *   host_loglik.cpp    log-likelihood blocks, pht_ctx_loglik* and pht_ctx_loglik_unif*
  *   host_predict.cpp   posterior-predictive replicates, pht_pred_* and pht_ctx_predict
  *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
+ *   host_estep.cpp     expected sufficient statistics: pht_ctx_estep, pht_estep_contract
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -238,6 +239,18 @@ struct pht_ctx {
   DevBuf<int> d_predflag, d_prednj;
   DevBuf<unsigned long long> d_predout;
   size_t predin_cap = 0, predy_cap = 0, predflag_cap = 0, prednj_cap = 0, predout_cap = 0;
+  /* pht_ctx_estep (allocated on first use; its own buffers and events, never
+   * the sampler's): one batch's int64 words [draw][class][k][G, T] and results
+   * [draw][Z n, N n n, E n]; the tables and totals are the log-likelihood's
+   * (d_lluin, d_llutab, d_lltot).  es_grid_cap: 0 = one block a CU
+   * (pht_ctx_estep_grid_cap); es_ms: the last call's device time, histograms
+   * (with the tables) and contraction */
+  DevBuf<long long> d_eswords;
+  DevBuf<double> d_esout;
+  size_t eswords_cap = 0, esout_cap = 0;
+  int es_grid_cap = 0;
+  float es_ms[2] = {0.f, 0.f};
+  Event es_ev[3];
 };
 
 namespace pht {
