@@ -246,6 +246,35 @@ int pht_estep_contract(int n, const double *S, const double *s, const long long 
 int pht_ctx_estep_grid_cap(pht_ctx *c, int cap);
 int pht_ctx_estep_ms(pht_ctx *c, float *hist_ms, float *contract_ms);
 
+/* Quantiles and residual-life quantiles (include/pht_quantile.h is the whole
+ * definition): per draw (S, s) with pi = e_1 and per probability p, the t >= t0
+ * with P(T <= t | T > t0) = p, by a safeguarded Newton iteration on the log
+ * survival function of pht_ctx_loglik_unif's evaluator.  No reference
+ * counterpart, and no observations are needed on the context.
+ *
+ * pht_ctx_quantile: ndraws draws as in pht_ctx_loglik_unif, `batch` (1..64) per
+ *   launch; np probabilities in any order, duplicates allowed; t0 >= 0 the
+ *   conditioning time (0: the plain quantile function); tmax > 0 the horizon
+ *   (+inf: as far as the table cap allows, 1400 / max_i -S_ii).  Outputs, each
+ *   ndraws * np in the caller's order of probs (all but t_out may be NULL):
+ *   t_out the quantile (t - t0 for t0 > 0, a residual life), lo_out and hi_out
+ *   the final bracket (absolute times), nev_out the evaluations of the root,
+ *   flags_out the PHT_Q_F_* bits; draw_flags_out (ndraws) as in
+ *   pht_ctx_loglik_unif.  p = 0 gives 0 and p = 1 +inf without a flag; a root
+ *   beyond the horizon +inf with PHT_Q_F_BEYOND; every other flag NaN.  The
+ *   buffers are the context's own: its chain and its WAIC state are not
+ *   affected.
+ * pht_ctx_quantile_ms: device time of the last call, the table kernel and the
+ *   searches.
+ * pht_quantile_host: host only (no GPU), one draw; bit for bit what the device
+ *   computes.  Returns the draw's flag word, < 0 on error. */
+int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const double *s, int np, const double *probs,
+                     double t0, double tmax, int batch, double *t_out, double *lo_out, double *hi_out, int *nev_out,
+                     unsigned *flags_out, int *draw_flags_out);
+int pht_ctx_quantile_ms(pht_ctx *c, float *table_ms, float *search_ms);
+int pht_quantile_host(int n, const double *S, const double *s, int np, const double *probs, double t0, double tmax,
+                      double *t_out, double *lo_out, double *hi_out, int *nev_out, unsigned *flags_out);
+
 /* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
  * the whole definition): per observation, from l[d, i] of every usable draw
  * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail

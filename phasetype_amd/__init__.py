@@ -29,7 +29,8 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "EVALUATORS", "evaluator_runs", "pred_table", "predict_finalise", "predict_combine", "rph",
            "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts", "loo", "loo_from_psis",
            "loo_compare", "PSIS_MAX_DRAWS", "estep_contract", "expected_stats", "complete_stats",
-           "em_step", "ph_em", "ESTEP_MAX_OBS"]
+           "em_step", "ph_em", "ESTEP_MAX_OBS", "qph", "pph", "dph", "ph_quantiles", "quantile_host",
+           "Q_F_P", "Q_F_T0", "Q_F_BEYOND", "Q_F_EVAL", "Q_F_CAP", "Q_F_DRAW"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -62,6 +63,7 @@ EXPORTS = [
     "pht_ctx_loo_begin", "pht_ctx_loo_fill", "pht_ctx_loo_fill_unif", "pht_ctx_loo", "pht_ctx_loo_end",
     "pht_estep_words", "pht_estep_yscale", "pht_ctx_estep", "pht_estep_contract", "pht_ctx_estep_grid_cap",
     "pht_ctx_estep_ms",
+    "pht_ctx_quantile", "pht_ctx_quantile_ms", "pht_quantile_host",
 ]
 
 
@@ -166,6 +168,10 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_estep_contract.argtypes = [C.c_int, _dp, _dp, _lp, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
     L.pht_ctx_estep_grid_cap.argtypes = [C.c_void_p, C.c_int]
     L.pht_ctx_estep_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_ctx_quantile.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp,
+                                   _dp, _dp, _ip, _up, _ip]
+    L.pht_ctx_quantile_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_quantile_host.argtypes = [C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _up]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -507,6 +513,42 @@ class Sweeper:
                    words=words.reshape(nd, 2, nw // 4, 2), yscale=ys)
         out["loglik"] = loglik_total(out["H"], out["F"], out["nbad"], flags != 0)
         return out
+
+    def quantile(self, S_list, s_list, probs, given: float = 0.0, tmax=None, batch: int = 64):
+        """pht_ctx_quantile: for each draw (S, s) and each probability p the
+        time t with P(T <= t | T > given) = p (include/pht_quantile.h), by a
+        safeguarded Newton iteration on the uniformisation evaluator's log
+        survival function; no observations are needed.
+
+        Returns ``t`` (the quantile; with ``given`` > 0 the residual life
+        t - given), ``lo`` and ``hi`` (the final bracket, absolute times),
+        ``nev`` (evaluations per root) and ``flags`` (Q_F_* bits), each
+        [draws, P] in the order of ``probs`` (any order, duplicates allowed),
+        and ``bad_draw`` / ``draw_flags`` per draw as ``loglik_unif`` gives
+        them.  p = 0 gives 0, p = 1 inf; a root beyond the horizon (``tmax``,
+        default and at most 1400 / the largest rate) is inf with Q_F_BEYOND;
+        any other flag is NaN.  ``last_quantile_ms`` then holds the device
+        time of the table kernel and of the searches."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd, n = S_all.shape[0], self.n
+        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
+            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        probs = np.ascontiguousarray(np.atleast_1d(probs), np.float64).reshape(-1)
+        P_ = len(probs)
+        if P_ < 1:
+            raise ValueError("need at least one probability")
+        t, lo, hi = np.zeros((nd, P_)), np.zeros((nd, P_)), np.zeros((nd, P_))
+        nev, flags = np.zeros((nd, P_), np.int32), np.zeros((nd, P_), np.uint32)
+        dflags = np.zeros(nd, np.int32)
+        if self.L.pht_ctx_quantile(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), P_, probs, float(given),
+                                   np.inf if tmax is None else float(tmax), int(batch), t.reshape(-1), lo.reshape(-1),
+                                   hi.reshape(-1), nev.reshape(-1), flags.reshape(-1), dflags) != 0:
+            raise _err(self.L)
+        tm, sm = C.c_float(0), C.c_float(0)
+        self.L.pht_ctx_quantile_ms(self.ctx, C.byref(tm), C.byref(sm))
+        self.last_quantile_ms = (tm.value, sm.value)
+        return dict(t=t, lo=lo, hi=hi, nev=nev, flags=flags, bad_draw=dflags != 0, draw_flags=dflags)
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
                 horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
@@ -1028,6 +1070,102 @@ def ph_curves(res, TT_or_T, grid, C_=None, n=None, device: int = 0, batch: int =
     finally:
         sw.close()
     return dict(logdens=ld, logsurv=ls, hazard=np.exp(ld - ls))
+
+
+# ------------------------------------------------- the d / p / q / r family
+# include/pht_quantile.h, phasetype_amd/csrc/pht_quantile.hip (no reference
+# counterpart); rph is further down with the posterior-predictive replicates
+Q_F_P, Q_F_T0, Q_F_BEYOND, Q_F_EVAL, Q_F_CAP, Q_F_DRAW = 1, 2, 4, 8, 16, 32
+
+
+def quantile_host(S, s, probs, given: float = 0.0, tmax=None) -> dict:
+    """pht_quantile_host (host only, no GPU): ``Sweeper.quantile``'s dict for
+    one draw, each array [P]; bit for bit what the device computes."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    probs = np.ascontiguousarray(np.atleast_1d(probs), np.float64).reshape(-1)
+    P_ = len(probs)
+    t, lo, hi = np.zeros(P_), np.zeros(P_), np.zeros(P_)
+    nev, flags = np.zeros(P_, np.int32), np.zeros(P_, np.uint32)
+    f = L.pht_quantile_host(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                            np.ascontiguousarray(s, np.float64).reshape(-1), P_, probs, float(given),
+                            np.inf if tmax is None else float(tmax), t, lo, hi, nev, flags)
+    if f < 0:
+        raise _err(L)
+    return dict(t=t, lo=lo, hi=hi, nev=nev, flags=flags, bad_draw=f != 0, draw_flags=f)
+
+
+def qph(S, s, p, given: float = 0.0, device: int = 0):
+    """The quantile function of PH(e_1, S): the t with P(T <= t) = p, or with
+    ``given`` = t0 > 0 the residual life t - t0 with P(T <= t | T > t0) = p
+    (Sweeper.quantile on one draw; the shape of ``p``).  inf for p = 1 and for
+    a root beyond 1400 / the largest rate; NaN for a p outside [0, 1]."""
+    S = np.asarray(S, np.float64)
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        r = sw.quantile([S], [s], np.asarray(p, np.float64).reshape(-1), given=given)
+        if r["bad_draw"][0]:
+            raise ValueError(f"not a usable generator (flag {r['draw_flags'][0]})")
+        t = r["t"][0].reshape(np.shape(p))
+        return float(t) if np.ndim(p) == 0 else t
+    finally:
+        sw.close()
+
+
+def _pointwise_unif(S, s, t, cens, device):
+    S = np.asarray(S, np.float64)
+    t = np.asarray(t, np.float64)
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        sw.set_obs(t.reshape(-1), np.full(t.size, cens, np.int32))
+        l = sw.loglik_unif([S], [s], pointwise=True)["pointwise"][0].reshape(t.shape)
+        return float(l) if t.ndim == 0 else l
+    finally:
+        sw.close()
+
+
+def dph(S, s, t, device: int = 0):
+    """The density of PH(e_1, S) at ``t``: exp of the uniformisation
+    evaluator's pointwise log-likelihood of exact observations."""
+    return np.exp(_pointwise_unif(S, s, t, 0, device))
+
+
+def pph(S, s, t, device: int = 0):
+    """The distribution function of PH(e_1, S) at ``t``: 1 - exp(log survival),
+    the evaluator's pointwise log-likelihood of censored observations."""
+    return -np.expm1(_pointwise_unif(S, s, t, 1, device))
+
+
+def ph_quantiles(res, TT_or_T, probs, given: float = 0.0, C_=None, n=None, burn: int = 0, thin: int = 1, tmax=None,
+                 device: int = 0, batch: int = 64, collation: str = "C", band=(.025, .5, .975)) -> dict:
+    """Posterior quantiles of a chain (``res`` and ``TT_or_T`` as in
+    ``log_lik``; rows ``burn::thin``): dict(q [draws, P], the quantile (or,
+    with ``given`` > 0, the residual-life quantile) of every draw at every
+    probability; band [len(band), P], the posterior ``band`` quantiles of each
+    column over its finite entries (NaN where none is); n_finite [P];
+    n_beyond [P], draws whose root lies beyond the horizon (inf in q);
+    n_flagged [P], draws that gave NaN (a flagged draw or root); flags
+    [draws, P], bad_draw [draws], lo, hi, nev).  Nothing is dropped silently:
+    n_finite + n_beyond + n_flagged = draws, but for p = 1 (inf, no flag)."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    try:
+        r = sw.quantile(S_list, s_list, probs, given=given, tmax=tmax, batch=batch)
+    finally:
+        sw.close()
+    q = r["t"]
+    fin = np.isfinite(q)
+    bands = np.full((len(band), q.shape[1]), np.nan)
+    for j in range(q.shape[1]):
+        if fin[:, j].any():
+            bands[:, j] = np.quantile(q[fin[:, j], j], band)
+    return dict(q=q, band=bands, n_finite=fin.sum(0), n_beyond=((r["flags"] & Q_F_BEYOND) != 0).sum(0),
+                n_flagged=np.isnan(q).sum(0), flags=r["flags"], bad_draw=r["bad_draw"], lo=r["lo"], hi=r["hi"],
+                nev=r["nev"], probs=np.atleast_1d(np.asarray(probs, np.float64)))
 
 
 # ------------------------------------------- expected statistics, EM fitting

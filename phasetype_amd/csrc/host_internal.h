@@ -15,6 +15,7 @@
  *   host_predict.cpp   posterior-predictive replicates, pht_pred_* and pht_ctx_predict
  *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
  *   host_estep.cpp     expected sufficient statistics: pht_ctx_estep, pht_estep_contract
+ *   host_quantile.cpp  quantiles and residual-life quantiles: pht_ctx_quantile, pht_quantile_host
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -251,6 +252,16 @@ struct pht_ctx {
   int es_grid_cap = 0;
   float es_ms[2] = {0.f, 0.f};
   Event es_ev[3];
+  /* pht_ctx_quantile (allocated on first use; its own buffers and events,
+   * never the sampler's or the WAIC state's): a call's sorted probabilities
+   * and horizons, one batch's results [t, lo, hi][draw][p] and [nev,
+   * flags][draw][p]; the draws and tables go through d_lluin and d_llutab as
+   * the E-step's do.  q_ms: the last call's device time, tables and searches */
+  DevBuf<double> d_qin, d_qout;
+  DevBuf<int> d_qouti;
+  size_t qin_cap = 0, qout_cap = 0, qouti_cap = 0;
+  float q_ms[2] = {0.f, 0.f};
+  Event q_ev[3];
 };
 
 namespace pht {
