@@ -15,10 +15,29 @@
  *   l = lmax y + log sum_i c_i exp((lambda_i - lmax) y),
  * so the far tail stays finite (the unshifted sum underflows to log 0).
  *
- * Only real, diagonalisable spectra are evaluated.  A draw whose dgeevx
- * fails, whose spectrum has a non-zero imaginary part or whose coefficients
- * are not finite carries a non-zero flag word and is never evaluated: its
- * log-likelihood is reported as NaN.
+ * Only real spectra are evaluated.  A draw whose dgeevx fails, whose spectrum
+ * has a non-zero imaginary part, whose generator is not finite or whose
+ * coefficients are ill-conditioned (below) carries a non-zero flag word and
+ * is never evaluated: its log-likelihood is reported as NaN.
+ *
+ * Contract.  The sum cancels: with A = sum_i |c_i| e_i / sum_i c_i e_i,
+ * e_i = exp((lambda_i - lmax) y), the rounding of the terms alone moves l by
+ * about 2^-52 A, and the coefficients of a defective or nearly defective
+ * spectrum (repeated or nearly equal rates: Erlang, a Coxian with one shared
+ * rate) are large with alternating signs.  Nothing in LAPACK's return says so.
+ * For every draw and observation the evaluator therefore returns one of two
+ * things: a value l with
+ *   |l - truth| <= E(A, l) = G 2^-52 A + 1e-13 |l| + ulp(l),
+ * or the report that there is none: the draw is flagged (value NaN), or the
+ * observation is bad for this draw (counted in nbad, pointwise NaN).  A finite
+ * value outside the bound is never returned.  The guard, per observation
+ * (pht_ll_finish): accabs = sum_i |c_i| e_i is accumulated beside acc, and the
+ * observation is bad when G 2^-52 accabs > E_max acc.  Per draw
+ * (pht_ll_illcond, in pht_loglik_build): the survival sum at y = 0, where the
+ * truth is 1, is already past the guard, G 2^-52 sum_i |b_i| > E_max, or a
+ * coefficient of a finite generator is not finite: PHT_LL_F_ILLCOND.
+ * G = PHT_LL_G and E_max = PHT_LL_EMAX are measured.
+ * acc and the bits of every accepted l do not depend on the guard.
  *
  * Every operation is explicit (fma where written, nothing else contracted:
  * every translation unit that includes this is compiled with
@@ -41,7 +60,18 @@ PHT_HD int pht_ll_off_b(int n) { return PHT_LL_DL + 2 * n; }
 /* flag word (0 = usable) */
 #define PHT_LL_F_INFO 1u      /* dgeevx / dgetrf / dgetri reported info != 0 */
 #define PHT_LL_F_COMPLEX 2u   /* an eigenvalue with a non-zero imaginary part */
-#define PHT_LL_F_NONFINITE 4u /* a non-finite eigenvalue or coefficient */
+#define PHT_LL_F_NONFINITE 4u /* a non-finite entry of the generator, or eigenvalue */
+/* (8u is PHT_LL_F_MU of include/pht_loglik_unif.h) */
+#define PHT_LL_F_ILLCOND 16u  /* coefficients past the cancellation guard at y = 0, or not finite */
+
+/* the cancellation guard: an observation is bad when
+ * (G 2^-52) accabs > E_max acc.  G: 4 times the worst
+ * (error - 1e-13 |l| - ulp(l)) / (2^-52 A) measured over the accepted values
+ * of tests/test_loglik.py, 90.1.  E_max: the largest power of two at or below
+ * 1e-6.  (DESIGN.md 5d has the figures.) */
+#define PHT_LL_G 361.0
+#define PHT_LL_EMAX 0x1p-20
+#define PHT_LL_GEPS (PHT_LL_G * 0x1p-52)
 
 /* totals per draw: int64 words [H, F, nbad, nobs] */
 #define PHT_LL_TOT 4
@@ -52,10 +82,20 @@ PHT_HD int pht_ll_off_b(int n) { return PHT_LL_DL + 2 * n; }
 /* one term of the shifted sum: acc + c exp(dl y) */
 PHT_HD double pht_ll_expterm(double dl, double y) { return pht_exp(dl * y); }
 
-/* l from the finished sum; *bad = 1 when the observation is bad for this
- * draw (acc <= 0, acc or l not finite, |l| >= 2^40), and the value is NaN */
-PHT_HD double pht_ll_finish(double lmax, double y, double acc, int *bad) {
-  const int ok_acc = (acc > 0.0) && (acc < INFINITY);
+/* the draw's flag from its survival coefficients: at y = 0 every e_i is 1 and
+ * the truth is 1, so the guard reads (G 2^-52) sum_i |b_i| > E_max (i
+ * increasing; a NaN or infinite sum is past it too) */
+PHT_HD int pht_ll_illcond(int n, const double *b) {
+  double sabs = 0.0;
+  for (int i = 0; i < n; i++) sabs = sabs + fabs(b[i]);
+  return !(PHT_LL_GEPS * sabs <= PHT_LL_EMAX);
+}
+
+/* l from the finished sums; *bad = 1 when the observation is bad for this
+ * draw (acc <= 0, acc or l not finite, |l| >= 2^40, or the sum cancelled past
+ * the guard: (G 2^-52) accabs > E_max acc), and the value is NaN */
+PHT_HD double pht_ll_finish(double lmax, double y, double acc, double accabs, int *bad) {
+  const int ok_acc = (acc > 0.0) && (acc < INFINITY) && (PHT_LL_GEPS * accabs <= PHT_LL_EMAX * acc);
   const double l = fma(lmax, y, pht_log(ok_acc ? acc : 1.0));
   const int ok = ok_acc && (fabs(l) < PHT_LL_HMAX);
   *bad = !ok;
@@ -66,9 +106,13 @@ PHT_HD double pht_ll_finish(double lmax, double y, double acc, int *bad) {
 PHT_HD double pht_ll_eval(int n, const double *blk, double y, int cens, int *bad) {
   const double *dl = blk + PHT_LL_DL;
   const double *c = blk + (cens ? pht_ll_off_b(n) : pht_ll_off_a(n));
-  double acc = 0.0;
-  for (int i = 0; i < n; i++) acc = fma(c[i], pht_ll_expterm(dl[i], y), acc);
-  return pht_ll_finish(blk[PHT_LL_LMAX], y, acc, bad);
+  double acc = 0.0, accabs = 0.0;
+  for (int i = 0; i < n; i++) {
+    const double e = pht_ll_expterm(dl[i], y);
+    acc = fma(c[i], e, acc);
+    accabs = fma(fabs(c[i]), e, accabs);
+  }
+  return pht_ll_finish(blk[PHT_LL_LMAX], y, acc, accabs, bad);
 }
 
 /* fixed-point words of a finite l, |l| < 2^40: l = h + f 2^-32 up to 2^-33 */

@@ -12,8 +12,13 @@
  *   Fbar(y) = pi exp(S y) 1 = sum_k Pois(k; mu y) ac_k,  ac_k = (R^k 1)_1
  * Every term is non-negative: no cancellation, and an error bound that does
  * not know the eigenvector conditioning,
- *   |l - truth| <= 2^-53 (n + 9) (k_hi + 1) + 2^-56,
- * k_hi the upper end of the observation's summation window.
+ *   |l - truth| <= 2^-53 (n + 9) (k_hi + 1) + 2^-56 + ulp(l),
+ * k_hi the upper end of the observation's summation window.  (The ulp(l) is
+ * the rounding of l itself to a double, which the series' bound does not
+ * know: at a tiny y, where k_hi is small and |l| large, it is the larger
+ * part.  Erlang(3), exact, y = 1e-9: l = -41.35 and k_hi = 2, the series' bound
+ * 4.0e-15, one ulp 7.1e-15, and with the rates 1e-12 apart the error is 1.3
+ * times the series' bound.)
  *
  * Per draw (pht_llu_meta, pht_llu_table): mu = max_i -S_ii (i increasing, from
  * 0), rinv = 1 / mu, R_ij = S_ij rinv, R_ii = fma(S_ii, rinv, 1) (as in

@@ -357,8 +357,12 @@ class Sweeper:
         [draws, pht_loglik_bytes(n)]) over this shard's observations.
 
         Returns ``H, F, nbad, nobs`` (int64 per draw), ``bad_draw`` (the
-        draw's flag word is non-zero: complex or defective spectrum, never
-        evaluated), ``total`` (``loglik_total`` of this shard's words) and,
+        draw's flag word is non-zero: a complex spectrum, a failed LAPACK call,
+        a non-finite generator, or coefficients that cancel past the guard of
+        include/pht_loglik.h, LL_F_ILLCOND, as a defective or nearly defective
+        spectrum gives; never evaluated), ``nbad`` counts the observations
+        that are bad for a usable draw (no density, or a sum that cancels
+        past the guard), ``total`` (``loglik_total`` of this shard's words) and,
         with ``pointwise``, l[draw, observation] in the caller's order.
         ``accumulate`` feeds the per-observation WAIC state (waic_state).
 
@@ -432,13 +436,17 @@ class Sweeper:
         see loglik_blocks for the result, which gains ``evaluator``: per draw,
         "spectral" or "unif".
 
-        ``evaluator``: "spectral" (the default; include/pht_loglik.h: a draw
-        with a complex or defective spectrum is NaN), "unif" (every draw by
-        uniformisation, include/pht_loglik_unif.h) or "auto" (spectral where
-        the draw's block is usable, uniformisation where its spectrum is
-        complex or defective, NaN only for a non-finite generator).  "auto"
-        issues one call per maximal run of draws of one evaluator, in draw
-        order, so the WAIC state sees the draws in their order.
+        ``evaluator``: "spectral" (the default; include/pht_loglik.h: a
+        flagged draw is NaN: a complex spectrum, or a defective or nearly
+        defective one whose coefficients cancel; an observation whose sum
+        cancels past the guard is bad, so the draw's total is -inf), "unif"
+        (every draw by uniformisation, include/pht_loglik_unif.h) or "auto"
+        (spectral where the draw's block is usable and no observation is bad,
+        uniformisation otherwise, NaN only for a non-finite generator).
+        "auto" first runs the usable blocks totals-only to find the draws with
+        bad observations, then issues one call per maximal run of draws of one
+        evaluator, in draw order, so the WAIC state sees each draw once and
+        in order.
         ``blocks``: the draws' spectral blocks where the caller has them."""
         if evaluator not in EVALUATORS:
             raise ValueError(f"evaluator must be one of {EVALUATORS}, got {evaluator!r}")
@@ -454,15 +462,26 @@ class Sweeper:
             out = self.loglik_blocks(blocks, **kw)
             out["evaluator"] = np.full(len(S_list), "spectral")
             return out
-        flags = np.ascontiguousarray(blocks[:, :8]).view(np.uint64).reshape(-1)
         parts = []
-        for lo, hi, unif in evaluator_runs(flags):
+        for lo, hi, unif in self._auto_runs(blocks, batch):
             r = (self.loglik_unif(S_list[lo:hi], s_list[lo:hi], **kw) if unif
                  else self.loglik_blocks(blocks[lo:hi], **kw))
             r.pop("flags", None)
             r["evaluator"] = np.full(hi - lo, "unif" if unif else "spectral")
             parts.append(r)
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+    def _auto_runs(self, blocks, batch: int = 64) -> list:
+        """evaluator_runs for evaluator="auto": a totals-only spectral pass
+        over the draws with a usable block (no WAIC accumulation, no pointwise
+        rows) finds those with bad observations; they go to uniformisation
+        with the flagged ones."""
+        flags = np.ascontiguousarray(blocks[:, :8]).view(np.uint64).reshape(-1)
+        nbad = np.zeros(len(flags), np.int64)
+        usable = np.flatnonzero(flags == 0)
+        if len(usable):
+            nbad[usable] = self.loglik_blocks(blocks[usable], batch=batch)["nbad"]
+        return evaluator_runs(flags, nbad)
 
     def estep(self, S_list, s_list, batch: int = 64, yscale=None, contract: bool = True, grid_cap: int = 0):
         """pht_ctx_estep: the expected sufficient statistics of each draw
@@ -678,7 +697,7 @@ class Sweeper:
         elif evaluator == "spectral":
             runs = [(0, nd, False)]
         else:
-            runs = evaluator_runs(np.ascontiguousarray(blocks[:, :8]).view(np.uint64).reshape(-1))
+            runs = self._auto_runs(blocks, batch)
         tot, bad = np.zeros((nd, 4), np.int64), np.zeros(nd, bool)
         which = np.full(nd, "spectral", dtype="<U8")
         self.loo_begin(nd)
@@ -883,22 +902,30 @@ def phtMCMC(x, states, beta, nu, zeta, n, mhit=1, resume=None, silent=False, col
 # No reference counterpart: the reference returns the draws only.  The
 # arithmetic is specified in include/pht_loglik.h and runs in
 # phasetype_amd/csrc/pht_loglik.hip: the spectral evaluator, the default (a
-# draw with a complex or defective spectrum is reported as NaN and never
-# evaluated).  The second evaluator, by uniformisation, serves those draws:
+# draw with a complex spectrum, or with a defective or nearly defective one
+# whose coefficients cancel past the guard, is flagged, reported as NaN and
+# never evaluated; an observation whose sum cancels past it is bad for that
+# draw).  The second evaluator, by uniformisation, serves those draws:
 # include/pht_loglik_unif.h, phasetype_amd/csrc/pht_loglik_unif.hip.
 EVALUATORS = ("spectral", "unif", "auto")
-LL_F_INFO, LL_F_COMPLEX, LL_F_NONFINITE, LL_F_MU = 1, 2, 4, 8  # flag words (pht_loglik.h, pht_loglik_unif.h)
+LL_F_INFO, LL_F_COMPLEX, LL_F_NONFINITE, LL_F_MU, LL_F_ILLCOND = 1, 2, 4, 8, 16  # flag words (pht_loglik.h, pht_loglik_unif.h)
 
 
-def evaluator_runs(flags) -> list:
+def evaluator_runs(flags, nbad=None) -> list:
     """evaluator="auto": the draw sequence split into maximal runs of one
     evaluator, in order, as [(lo, hi, unif)] over draws [lo, hi).  ``flags``:
     the draws' spectral block flag words.  A draw goes to uniformisation where
-    its spectrum is complex or defective (LL_F_COMPLEX, LL_F_INFO) and its
-    generator finite; otherwise to the spectral evaluator (flag 0: evaluated;
-    LL_F_NONFINITE: NaN from either)."""
+    its spectrum is complex, defective or so nearly defective that its
+    coefficients cancel (LL_F_COMPLEX, LL_F_INFO, LL_F_ILLCOND) and its
+    generator finite, and where its block is usable but its spectral
+    evaluation left bad observations (``nbad``: per draw, from a totals-only
+    spectral pass; None: not looked at); otherwise to the spectral evaluator
+    (flag 0: evaluated; LL_F_NONFINITE: NaN from either)."""
     flags = np.asarray(flags).astype(np.uint64).reshape(-1)
-    unif = ((flags & np.uint64(LL_F_INFO | LL_F_COMPLEX)) != 0) & ((flags & np.uint64(LL_F_NONFINITE)) == 0)
+    unif = (((flags & np.uint64(LL_F_INFO | LL_F_COMPLEX | LL_F_ILLCOND)) != 0)
+            & ((flags & np.uint64(LL_F_NONFINITE)) == 0))
+    if nbad is not None:
+        unif = unif | ((flags == 0) & (np.asarray(nbad).reshape(-1) > 0))
     runs, lo = [], 0
     for k in range(1, len(unif) + 1):
         if k == len(unif) or unif[k] != unif[lo]:
@@ -909,8 +936,10 @@ def evaluator_runs(flags) -> list:
 
 def loglik_block(S, s) -> np.ndarray:
     """One draw's block for ``Sweeper.loglik_blocks`` (pht_loglik_build; host
-    only): uint8[pht_loglik_bytes(n)].  An unusable draw (complex or defective
-    spectrum, non-finite entry) has a non-zero first word."""
+    only): uint8[pht_loglik_bytes(n)].  An unusable draw (complex spectrum,
+    failed LAPACK call, non-finite entry, or coefficients that cancel past
+    the guard, LL_F_ILLCOND: every exactly defective spectrum and the nearly
+    defective ones) has a non-zero first word."""
     L = load()
     S = np.asarray(S, np.float64)
     n = S.shape[0]
@@ -1007,10 +1036,12 @@ def log_lik(res, x, TT_or_T=None, censored=None, C_=None, n=None, device: int = 
     ``res`` (the dict phtMCMC2 / phtMCMC return, or the array of
     Sweeper.gibbs), over data ``x`` / ``censored``.  ``TT_or_T``: the matrix of
     variable names given to phtMCMC2 (numbered as it numbers them; default the
-    chain's own) or the integer matrix T of Sweeper.gibbs.  NaN for a draw with
-    a complex or defective spectrum, -inf where an observation has no density.
-    ``evaluator`` (Sweeper.loglik): "unif" or "auto" evaluate the draws with a
-    complex or defective spectrum too, by uniformisation."""
+    chain's own) or the integer matrix T of Sweeper.gibbs.  NaN for a flagged
+    draw (a complex spectrum; a defective or nearly defective one, as every
+    draw of a structure with one rate on several transitions has:
+    LL_F_ILLCOND), -inf where an observation has no density or its sum cancels
+    past the guard.  ``evaluator`` (Sweeper.loglik): "unif" or "auto" evaluate
+    those draws too, by uniformisation."""
     S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
     sw = _obs_sweeper(x, censored, n, device)
     try:
@@ -1035,8 +1066,8 @@ def waic(res, x, TT_or_T=None, censored=None, C_=None, n=None, burn: int = 0, de
          collation: str = "C", evaluator: str = "spectral") -> dict:
     """WAIC of a chain (rows from ``burn`` on) over data ``x`` / ``censored``:
     dict(elpd_waic, p_waic, lppd, waic, pointwise=(lppd_i, p_waic_i),
-    n_draws_used).  Draws with a complex or defective spectrum are left out by
-    the default ``evaluator``; "auto" (Sweeper.loglik) evaluates them by
+    n_draws_used).  Flagged draws (a complex spectrum, or coefficients that
+    cancel: Sweeper.loglik_blocks) are left out by the default ``evaluator``; "auto" (Sweeper.loglik) evaluates them by
     uniformisation, in the chain's order, and n_draws_used then counts every
     finite draw."""
     S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)

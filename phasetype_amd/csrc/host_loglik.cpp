@@ -5,8 +5,11 @@
  * else.  Two evaluators, chosen per call.  Spectral (specification in
  * include/pht_loglik.h, kernel pht_loglik.hip; pht_loglik_build +
  * pht_ctx_loglik): a draw whose spectrum is complex (the sampler warns and
- * uses the real parts, as the reference does), whose LAPACK call fails or
- * whose coefficients are not finite is flagged and never evaluated.
+ * uses the real parts, as the reference does), whose LAPACK call fails,
+ * whose generator is not finite or whose coefficients cancel past the guard
+ * of pht_loglik.h (a defective or nearly defective spectrum: LAPACK does not
+ * report those) is flagged and never evaluated; an observation whose sum
+ * cancels past the guard is bad for that draw.
  * Uniformisation (include/pht_loglik_unif.h, pht_loglik_unif.hip;
  * pht_ctx_loglik_unif): any finite generator, straight from (S, s), no LAPACK.
  * pht_ctx_loo_fill / pht_ctx_loo_fill_unif are the same two calls with their
@@ -103,11 +106,17 @@ extern "C" int pht_loglik_build(int n, const double *S, const double *s, unsigne
     for (int i = 0; i < n; i++) {
       const double piQ = Q[0 + i * n]; /* pi = e_1 */
       const double dl = ev[i] - lmax, a = piQ * Qs[i], b = piQ * Q1[i];
-      if (!std::isfinite(ev[i]) || !std::isfinite(a) || !std::isfinite(b)) flag |= PHT_LL_F_NONFINITE;
+      if (!std::isfinite(ev[i])) flag |= PHT_LL_F_NONFINITE;
+      /* (a finite generator: the solve against a singular Q overflowed) */
+      if (!std::isfinite(a) || !std::isfinite(b)) flag |= PHT_LL_F_ILLCOND;
       w[PHT_LL_DL + i] = dl;
       w[pht_ll_off_a(n) + i] = a;
       w[pht_ll_off_b(n) + i] = b;
     }
+    /* a defective or nearly defective spectrum: LAPACK returns info = 0 and
+     * the pivots are not zero, but the survival sum cancels past the guard
+     * already at y = 0 */
+    if (pht_ll_illcond(n, w.data() + pht_ll_off_b(n))) flag |= PHT_LL_F_ILLCOND;
   }
   if (flag) std::fill(w.begin(), w.end(), 0.0);
   memcpy(out, w.data(), 8 * (size_t)words);

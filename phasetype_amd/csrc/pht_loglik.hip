@@ -5,8 +5,9 @@
  * One lane per observation, tiles of 256 over a capped grid.  The launch's
  * draw blocks (up to kLoglikBatch) are staged once per workgroup in LDS; a
  * block's words are the same for every lane, so its reads are broadcasts.
- * Per draw a lane evaluates l (the n exponentials first, then the dependent
- * fma chain), updates its private WAIC state and contributes (h, f, bad, obs)
+ * Per draw a lane evaluates l (the n exponentials first, then the two
+ * dependent fma chains: the sum and the cancellation guard's sum of absolute
+ * terms), updates its private WAIC state and contributes (h, f, bad, obs)
  * to the draw's totals: wave shuffles, then one LDS add per wave, and at the
  * end of the block one 64-bit integer atomic per word and draw.  Integer sums:
  * the totals do not depend on the grid, the tiling or the batch.
@@ -65,18 +66,25 @@ __global__ void __launch_bounds__(kLoglikBlock) loglik_kernel(const LoglikArgs a
       }
       const double *dl = blk + PHT_LL_DL;
       const double *c = blk + PHT_LL_DL + (cens ? 2 * n : n);
-      double acc = 0.0;
+      double acc = 0.0, accabs = 0.0; /* accabs: the cancellation guard's sum of |c_i| e_i */
       if constexpr (NT > 0) {
         double e[NT > 0 ? NT : 1];
 #pragma unroll
         for (int i = 0; i < NT; i++) e[i] = pht_ll_expterm(dl[i], y);
 #pragma unroll
-        for (int i = 0; i < NT; i++) acc = fma(c[i], e[i], acc);
+        for (int i = 0; i < NT; i++) {
+          acc = fma(c[i], e[i], acc);
+          accabs = fma(fabs(c[i]), e[i], accabs);
+        }
       } else {
-        for (int i = 0; i < n; i++) acc = fma(c[i], pht_ll_expterm(dl[i], y), acc);
+        for (int i = 0; i < n; i++) {
+          const double e = pht_ll_expterm(dl[i], y);
+          acc = fma(c[i], e, acc);
+          accabs = fma(fabs(c[i]), e, accabs);
+        }
       }
       int bad;
-      const double l = pht_ll_finish(blk[PHT_LL_LMAX], y, acc, &bad);
+      const double l = pht_ll_finish(blk[PHT_LL_LMAX], y, acc, accabs, &bad);
       long long h = 0, f = 0, bo = 0; /* bo: bad << 32 | obs (a wave adds at most 64 of each) */
       if (live) {
         if (bad) {

@@ -5,8 +5,9 @@
  */
 #include "pht_loglik.h"
 
-/* l[i] for every observation from one draw block (NaN where bad, and for
- * every observation of a flagged block) */
+/* l[i] for every observation from one draw block (NaN where bad, the
+ * cancellation guard of pht_ll_finish included, and for every observation of
+ * a flagged block) */
 void spec_pointwise(int n, const double *blk, long count, const double *y, const int *cens, double *l) {
   uint64_t flag;
   memcpy(&flag, blk + PHT_LL_FLAG, 8);

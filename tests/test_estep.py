@@ -24,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import estep_ref as R  # noqa: E402
+import evaluator_cases as EC  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
 from phasetype_amd.synth import bd_exit, simulate_ph  # noqa: E402
@@ -75,6 +76,38 @@ def test_restatement_against_mpmath(name):
         assert err <= b[k], (name, k, err, b[k])
     # the window's l is the evaluator's, and both are the truth's
     assert np.max(np.abs(r["l"] - m["l"])) <= np.max(U.bound(n, r["khi"]))
+
+
+# off BD-exit (tests/evaluator_cases.py): one generator per family whose real
+# spectrum is defective, nearly defective or stiff, on its grid of y from 1e-9
+# to 60, each exact and censored
+OFF_BD = {
+    "erlang3": lambda: EC.erlang(3),
+    "coxian_shared6": lambda: EC.coxian_shared(6),
+    "gapped3": lambda: EC.gapped(3, eps=1e-9),
+    "hypoexp6": lambda: EC.hypoexp(6),
+    "stiff6": lambda: EC.stiff(6),
+}
+
+
+@pytest.mark.parametrize("name", list(OFF_BD))
+def test_restatement_against_mpmath_off_bd_exit(name):
+    """The same check on the series the evaluators share, where the spectral
+    evaluator gives up.  The truth's digits grow with n and -log10 y: an entry
+    of the block exponential is as small as y^(2 n - 1) and expm's error is
+    absolute."""
+    S, s = OFF_BD[name]()
+    n = S.shape[0]
+    y, cens = EC.observations(S)
+    r = R.estep(S, s, y, cens)
+    assert r["flag"] == 0 and r["nbad"] == 0
+    m = R.mp_reference(S, s, y, cens, dps=60 + 6 * n * 9 + int(np.max(-np.diag(S)) * y.max() / np.log(10.0)))
+    b = R.bounds(n, y, cens, r["klo"], r["khi"], np.ones(len(y), bool), r["yscale"])
+    for k in "ZNEA":
+        err = float(np.max(np.abs(r[k] - m[k])))
+        print(f"{name} {k}: max error {err:.3e}, bound {b[k]:.3e}, fraction {err / b[k]:.4f}")
+        assert err <= b[k], (name, k, err, b[k])
+    assert np.all(np.abs(r["l"] - m["l"]) <= U.bound(n, r["khi"], r["l"]))
 
 
 @pytest.mark.parametrize("name", list(CASES))

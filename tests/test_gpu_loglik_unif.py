@@ -13,6 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import loglik_ref as R  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -77,6 +78,29 @@ def test_pointwise_bit_exact(gpu, n):
     assert np.array_equal(_bits(got["pointwise"]), _bits(want))
     assert np.array_equal(_words(got), R.totals(want))
     assert not got["bad_draw"].any() and not got["flags"].any() and np.all(np.isfinite(got["total"]))
+
+
+@pytest.mark.parametrize("n", [3, 10])
+@pytest.mark.parametrize("family", EC.FAMILIES)
+def test_pointwise_bit_exact_off_bd_exit(gpu, family, n):
+    """Real spectra off BD-exit (tests/evaluator_cases.py: stiff, defective
+    and nearly defective among them), scaled by 0.8 .. 1.25, over 65
+    observations from y = 1e-9 to 60, exact and censored interleaved: batch 1
+    and 64, totals-only and pointwise, no observation bad."""
+    S, s = EC.generator(family, n, **({"eps": 1e-3} if family == "gapped" else {}))
+    Ss, ss = U.scaled(S, s)
+    y, cens = EC.tiled(*EC.observations(S, scale=max(U.SCALES)), 65)
+    want = U.pointwise(Ss, ss, y, cens)
+    assert np.all(np.isfinite(want))
+    sw = _sweeper(n, y, cens)
+    for batch in (1, 64):
+        got = sw.loglik_unif(Ss, ss, batch=batch)
+        assert np.array_equal(_words(got), R.totals(want)), batch
+        got = sw.loglik_unif(Ss, ss, batch=batch, pointwise=True)
+        assert np.array_equal(_bits(got["pointwise"]), _bits(want)), batch
+        assert np.array_equal(_words(got), R.totals(want)), batch
+        assert not got["flags"].any() and np.all(np.isfinite(got["total"]))
+    sw.close()
 
 
 @pytest.mark.parametrize("N", [1, 63, 64, 65, 257])

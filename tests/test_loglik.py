@@ -4,6 +4,12 @@ host entry points and the tests' restatement (tests/loglik_spec.c); no GPU.
 * pht_loglik_build + restatement against mpmath.expm at 50 digits, within
   64 * 2^-52 * cond2(Q) + 1e-13 * |l| (Q from numpy.linalg.eig(S)): the
   spectral sum loses cond(Q) ulps, the lmax y shift a few ulps of |l|.
+* The contract off BD-exit (tests/evaluator_cases.py: the structures, stiff
+  rates, Erlang, shared-rate Coxian, nearly equal rates, hypoexponential, at
+  y from 1e-9 to 60): every value the evaluator returns is within
+  E(A, l) = G 2^-52 A + 1e-13 |l| + ulp(l) of mpmath, everything else is a
+  flagged draw or a counted bad observation; the guard rejects what it must
+  and nothing of the well-conditioned list.
 * Complex spectra and non-finite generators are flagged, never evaluated.
 * The fixed-point totals are exact integer sums: within N * 2^-33 of
   math.fsum, identical under permutation.
@@ -20,6 +26,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import loglik_ref as R  # noqa: E402
 import phasetype_amd as P  # noqa: E402
 from phasetype_amd.synth import bd_exit, simulate_ph  # noqa: E402
@@ -72,6 +79,145 @@ def test_block_and_restatement_against_mpmath(lib, n):
         worst = max(worst, err / bound)
         assert err <= bound, (n, li, float(ti), err, bound)
     print(f"n={n}: cond2(Q)={cond:.3g}, worst error / bound = {worst:.3g}")
+    # the contract's bound holds here too, and its ratio is measured: PHT_LL_G is 4 times the worst
+    A = EC.spectral_A(blk, y, cens)
+    ratio = 0.0
+    for li, ti, Ai in zip(l, truth, A):
+        err = float(abs(mp.mpf(float(li)) - ti))
+        assert err <= EC.spectral_bound(Ai, ti), (n, li, float(ti), err, Ai)
+        ratio = max(ratio, (err - 1e-13 * abs(float(ti)) - EC.ulp(ti)) / (2.0 ** -52 * Ai))
+    print(f"n={n}: worst (error - 1e-13 |l| - ulp) / (2^-52 A) = {ratio:.3g}, worst 2^-52 A = {2.0 ** -52 * A.max():.3g}")
+
+
+_CONTRACT = {}
+
+
+def _contract(case):
+    """One case through loglik_block, the restatement and the truth: dict(flag,
+    y, cens, l, A, err, bound, tot); the contract is asserted here, once per
+    case (the must lists below read the same record)."""
+    import mpmath as mp
+
+    key = EC.case_id(case)
+    if key in _CONTRACT:
+        return _CONTRACT[key]
+    family, n, kw = case
+    S, s = EC.generator(family, n, **kw)
+    y, cens = EC.observations(S)
+    blk = P.loglik_block(S, s)
+    flag = int(blk[:8].view(np.uint64)[0])
+    l = R.pointwise(blk[None, :], y, cens)[0]
+    tot = R.totals(l[None, :])[0]
+    rec = dict(flag=flag, y=y, cens=cens, l=l, tot=tot, A=np.full(len(y), np.nan), err=np.full(len(y), np.nan),
+               bound=np.full(len(y), np.nan))
+    if flag:
+        assert np.all(np.isnan(l)), (key, "a flagged draw is never evaluated")
+    else:
+        truth = EC.truths(S, s, y, cens)
+        rec["A"] = EC.spectral_A(blk, y, cens)
+        for k in np.flatnonzero(np.isfinite(l)):
+            rec["err"][k] = float(abs(mp.mpf(float(l[k])) - truth[k]))
+            rec["bound"][k] = EC.spectral_bound(rec["A"][k], truth[k])
+        # a rejected pair is reported: NaN pointwise and counted
+        assert tot[2] == np.sum(np.isnan(l)) and tot[3] == np.sum(np.isfinite(l)), (key, tot)
+        assert not np.any(np.isinf(l)), key
+    fin = np.isfinite(l)
+    ratio = (np.max((rec["err"][fin] - 1e-13 * np.abs(l[fin]) - np.spacing(np.abs(l[fin])))
+                    / (2.0 ** -52 * rec["A"][fin])) if fin.any() else float("nan"))
+    rec["ratio"] = ratio
+    print(f"{key}: flag {flag}, accepted {int(fin.sum())} of {len(y)}, worst error "
+          f"{np.max(rec['err'][fin]) if fin.any() else float('nan'):.3g}, worst error / bound "
+          f"{np.max(rec['err'][fin] / rec['bound'][fin]) if fin.any() else float('nan'):.3g}, "
+          f"worst 2^-52 A accepted {2.0 ** -52 * np.max(rec['A'][fin]) if fin.any() else float('nan'):.3g}, "
+          f"worst (error - 1e-13 |l| - ulp) / (2^-52 A) {ratio:.3g}")
+    _CONTRACT[key] = rec
+    for k in np.flatnonzero(fin):
+        assert rec["err"][k] <= rec["bound"][k], (key, y[k], cens[k], l[k], rec["err"][k], rec["bound"][k])
+    return rec
+
+
+def test_header_constants_are_the_tests():
+    import re
+
+    with open(os.path.join(os.path.dirname(HERE), "include", "pht_loglik.h")) as f:
+        h = f.read()
+    assert float(re.search(r"#define PHT_LL_G ([0-9.]+)", h).group(1)) == EC.G
+    assert float.fromhex(re.search(r"#define PHT_LL_EMAX (\S+)", h).group(1)) == EC.E_MAX <= 1e-6
+    assert re.search(r"#define PHT_LL_F_ILLCOND 16u", h) and P.LL_F_ILLCOND == 16
+
+
+@pytest.mark.parametrize("case", EC.CASES, ids=EC.case_id)
+def test_spectral_contract_off_bd_exit(lib, case):
+    """loglik_block, then the restatement, against the truth: every finite
+    value within E(A, l) (A recomputed in numpy from the block), every other
+    pair a flagged draw or a NaN counted in nbad.  PHT_LL_G is 4 times the
+    worst (error - 1e-13 |l| - ulp(l)) / (2^-52 A) this test and
+    test_block_and_restatement_against_mpmath print over the accepted pairs:
+    90.1, at bd_exit(20), y = 13.0, exact."""
+    _contract(case)
+
+
+def test_guard_accepts_the_well_conditioned_list(lib):
+    """The guard may not hide failures.  No draw of bd_exit(n) at this file's
+    inputs, nor of acyclic, reversible and stiff at n = 6 and 12 with
+    y >= 1e-3, is flagged, and none of their observations is bad.
+
+    PHT_LL_EMAX is the largest power of two below 1e-6.  With 16 times the
+    measured A the list would still be accepted in full, except bd_exit(20):
+    its 2^-52 A reaches 7.8e-10 (y = 1e-9, exact; 6.6e-10 at y = 0.08), which
+    G = 361 leaves 3.4 times below the guard, and no power of two below 1e-6
+    leaves 16.  That headroom is printed, the 16 asserted for the rest."""
+    worst = {}
+    for n in (3, 5, 10, 15, 20):
+        S, s, y, cens = _inputs(n)
+        blk = P.loglik_block(S, s)
+        assert blk[:8].view(np.uint64)[0] == 0
+        assert np.all(np.isfinite(R.pointwise(blk[None, :], y, cens)[0]))
+        worst[f"bd-{n}"] = float(np.max(EC.spectral_A(blk, y, cens)))
+    for family in ("acyclic", "reversible", "stiff"):
+        for n in EC.STRUCT_N:
+            rec = _contract((family, n, {}))
+            keep = rec["y"] >= 1e-3
+            assert rec["flag"] == 0 and np.all(np.isfinite(rec["l"][keep])), (family, n)
+            worst[f"{family}-{n}"] = float(np.max(rec["A"][keep]))
+    for key, A in worst.items():
+        room = EC.E_MAX / (EC.G * 2.0 ** -52 * A)
+        print(f"{key}: worst 2^-52 A = {2.0 ** -52 * A:.3g}, {room:.3g} times below the guard")
+        assert room >= (16.0 if key != "bd-20" else 1.0), (key, room)
+
+
+def test_guard_rejects_the_ill_conditioned_list(lib):
+    """Erlang and the shared-rate Coxian (exactly defective) are flagged
+    ILLCOND at every n; with nearly equal rates (n = 6, 10, every eps) and at
+    hypoexp(3), y = 1e-9 (f = 6e-18 from coefficients of order one) every
+    observation is rejected or within the bound.  The rows that were finite
+    and wrong by tens of nats (gapped n = 6, eps = 1e-3; n = 10, eps = 1e-9)
+    are rejected."""
+    for family in ("erlang", "coxian_shared"):
+        for n in EC.NEW_N:
+            rec = _contract((family, n, {}))
+            assert rec["flag"] & P.LL_F_ILLCOND and not rec["flag"] & P.LL_F_NONFINITE, (family, n, rec["flag"])
+    for n in (6, 10):
+        for eps in EC.EPS:
+            rec = _contract(("gapped", n, {"eps": eps}))  # (asserts the bound on whatever is finite)
+            assert rec["flag"] or rec["tot"][2] + rec["tot"][3] == len(rec["y"])
+    for n, eps in ((6, 1e-3), (10, 1e-9)):
+        assert _contract(("gapped", n, {"eps": eps}))["flag"] & P.LL_F_ILLCOND
+    rec = _contract(("hypoexp", 3, {}))
+    k = np.flatnonzero((rec["y"] == 1e-9) & (rec["cens"] == 0))[0]
+    assert rec["flag"] == 0 and (np.isnan(rec["l"][k]) or rec["err"][k] <= rec["bound"][k])
+    assert rec["tot"][2] >= 1, "at HEAD this value was finite with nothing behind it"
+
+
+def test_erlang_closed_forms_guard_the_truth():
+    """The expm truth against log f = n log lam + (n - 1) log y - lam y -
+    log (n - 1)! and the Poisson-sum survival, to 1e-25 relative."""
+    for n in EC.NEW_N:
+        S, s = EC.erlang(n)
+        y, cens = EC.observations(S)
+        for yi, ci in zip(y, cens):
+            t, c = EC.truth(S, s, float(yi), int(ci)), EC.erlang_closed(n, EC.LAM, float(yi), int(ci))
+            assert abs(t - c) <= 1e-25 * abs(c), (n, yi, ci, t, c)
 
 
 def test_far_tail_is_finite(lib):

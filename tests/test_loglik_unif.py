@@ -9,8 +9,12 @@
   wrong by 3e-8.
 * Real spectra: agreement with the spectral restatement within the sum of the
   two evaluators' bounds.
+* Every family of tests/evaluator_cases.py (real spectra off BD-exit, the
+  defective and nearly defective ones included) against the truth, within the
+  bound plus one ulp(l).
 * Table sanity, the table cap, draw flags, the K rule.
-* The run splitter of evaluator="auto".
+* The run splitter of evaluator="auto", and its routing of ill-conditioned
+  draws and of draws with a bad observation.
 """
 import math
 import os
@@ -22,6 +26,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import loglik_ref as R  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -132,6 +137,75 @@ def test_real_spectra_agree_with_the_spectral_evaluator(lib, n):
     print(f"n={n}: worst |spectral - unif| / (sum of bounds) = {worst:.3g}")
 
 
+@pytest.mark.parametrize("case", EC.CASES, ids=EC.case_id)
+def test_unif_on_real_spectra(case):
+    """The restatement on every family of tests/evaluator_cases.py (real
+    spectra: well conditioned, stiff, defective, nearly defective), y from
+    1e-9 to 60, against the truth: within the a-priori bound plus one ulp(l),
+    no observation bad.  Without the ulp(l) three pairs miss, all exact at
+    y = 1e-9 on an Erlang chain with the rates 1e-12 or 1e-9 apart: n = 3
+    (l = -41.35, k_hi = 2) by a factor 1.28, n = 6 and 10 by 1.01 and 1.02;
+    Erlang(3) itself is at 0.91."""
+    import mpmath as mp
+
+    family, n, kw = case
+    S, s = EC.generator(family, n, **kw)
+    y, cens = EC.observations(S)
+    l, khi = U.pointwise([S], [s], y, cens, with_khi=True)
+    assert np.all(np.isfinite(l)), (EC.case_id(case), "no observation is bad", y[~np.isfinite(l[0])])
+    truth = EC.truths(S, s, y, cens)
+    err = np.array([float(abs(mp.mpf(float(li)) - ti)) for li, ti in zip(l[0], truth)])
+    series, full = U.bound(n, khi[0]), U.bound(n, khi[0], l[0])
+    k = int(np.argmax(err / series))
+    print(f"{EC.case_id(case)}: worst error / (bound + ulp) = {np.max(err / full):.3g}; worst error / series bound "
+          f"= {err[k] / series[k]:.3g} at y = {y[k]:g}, cens = {cens[k]}, l = {l[0][k]:.6g}, k_hi = {khi[0][k]}")
+    assert np.all(err <= full), (EC.case_id(case), y[err > full], err[err > full], full[err > full])
+
+
+def test_auto_routes_ill_conditioned_draws(lib):
+    """evaluator="auto" on bd, Erlang, nearly equal rates, a complex spectrum,
+    a non-finite generator and a well-conditioned chain with a bad observation
+    (hypoexp(3) at y = 1e-9): the flagged draws and the one with nbad > 0 go
+    to uniformisation, and every finite-generator draw ends within its
+    evaluator's bound of the truth."""
+    import mpmath as mp
+
+    bdS, bds = EC.generator("bd", 3)
+    nonfin = bdS.copy()
+    nonfin[1, 0] = np.nan
+    draws = [(bdS, bds), EC.erlang(3), EC.gapped(6, eps=1e-3), U.CYCLIC, (nonfin, bds), EC.hypoexp(3), (bdS, bds)]
+    obs = [EC.observations(bdS if k == 4 else S) for k, (S, s) in enumerate(draws)]
+    blocks = [P.loglik_block(S, s) for S, s in draws]
+    flags = np.array([int(b[:8].view(np.uint64)[0]) for b in blocks], np.uint64)
+    assert flags[0] == 0 and flags[1] & P.LL_F_ILLCOND and flags[2] & P.LL_F_ILLCOND
+    assert flags[3] & P.LL_F_COMPLEX and flags[4] == P.LL_F_NONFINITE and flags[5] == 0
+    spectral = [R.pointwise(b[None, :], y, c)[0] for b, (y, c) in zip(blocks, obs)]
+    nbad = np.array([R.totals(l[None, :])[0][2] if f == 0 else 0 for l, f in zip(spectral, flags)])
+    assert nbad.tolist() == [0, 0, 0, 0, 0, nbad[5], 0] and nbad[5] > 0
+    # without the spectral pre-pass hypoexp(3) stays spectral (total -inf)
+    assert P.evaluator_runs(flags) == [(0, 1, False), (1, 4, True), (4, 7, False)]
+    runs = P.evaluator_runs(flags, nbad)
+    assert runs == [(0, 1, False), (1, 4, True), (4, 5, False), (5, 6, True), (6, 7, False)]
+    for lo, hi, unif in runs:
+        for d in range(lo, hi):
+            (S, s), (y, cens) = draws[d], obs[d]
+            if d == 4:
+                assert np.all(np.isnan(spectral[d]))
+                assert np.all(np.isnan(U.pointwise([S], [s], y, cens)))
+                continue
+            truth = EC.truths(S, s, y, cens)
+            if unif:
+                l, khi = U.pointwise([S], [s], y, cens, with_khi=True)
+                bounds = U.bound(S.shape[0], khi[0], l[0])
+                l = l[0]
+            else:
+                l = spectral[d]
+                bounds = [EC.spectral_bound(A, t) for A, t in zip(EC.spectral_A(blocks[d], y, cens), truth)]
+            assert np.all(np.isfinite(l)), (d, unif)
+            for li, ti, bi in zip(l, truth, bounds):
+                assert float(abs(mp.mpf(float(li)) - ti)) <= bi, (d, unif, li, float(ti), bi)
+
+
 @pytest.mark.parametrize("name", ["CYCLIC", "ring10", "ring20"])
 def test_table_sanity(name):
     S, s = CASES[name]()
@@ -202,3 +276,9 @@ def test_evaluator_runs():
     runs = P.evaluator_runs(np.array([0, F, F, 0, 0, F], np.uint64))
     assert [r[0] for r in runs] == [0, 1, 3, 5] and [r[1] for r in runs] == [1, 3, 5, 6]
     assert P.EVALUATORS == ("spectral", "unif", "auto")
+    # ill-conditioned coefficients go to uniformisation like a complex spectrum; so does a usable block with a
+    # bad observation once the spectral pre-pass has counted it (a flagged draw's count is not looked at)
+    I = P.LL_F_ILLCOND
+    assert P.evaluator_runs([0, I, F | I, I | P.LL_F_NONFINITE]) == [(0, 1, False), (1, 3, True), (3, 4, False)]
+    assert P.evaluator_runs([0, 0, F, P.LL_F_NONFINITE], [0, 2, 0, 5]) == [(0, 1, False), (1, 3, True), (3, 4, False)]
+    assert P.evaluator_runs([0, 0], [0, 0]) == P.evaluator_runs([0, 0]) == [(0, 2, False)]

@@ -21,6 +21,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import quantile_ref as Q  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -44,6 +45,13 @@ CASES = {
     "ring5": lambda: U.ring(5),
     "ring10_s123_zero": _ring10_zeros,
     "n1": lambda: (np.array([[-0.7]]), np.array([0.7])),
+    # off BD-exit (tests/evaluator_cases.py): real spectra that are defective or nearly defective (the
+    # stiff family is not here: its median lies beyond the horizon, PHT_Q_F_BEYOND, as documented)
+    "erlang6": lambda: EC.erlang(6),
+    "coxian_shared6": lambda: EC.coxian_shared(6),
+    "gapped6": lambda: EC.gapped(6, eps=1e-9),
+    "hypoexp6": lambda: EC.hypoexp(6),
+    "neareq6": lambda: EC.generator("neareq", 6),
 }
 PROBS = np.array([1e-6, 1e-3, 0.1, 0.5, 0.9, 1 - 1e-9])
 _CACHE = {}
