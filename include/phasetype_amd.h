@@ -275,6 +275,51 @@ int pht_ctx_quantile_ms(pht_ctx *c, float *table_ms, float *search_ms);
 int pht_quantile_host(int n, const double *S, const double *s, int np, const double *probs, double t0, double tmax,
                       double *t_out, double *lo_out, double *hi_out, int *nev_out, unsigned *flags_out);
 
+/* Fleet forecasts (include/pht_forecast.h is the whole definition): for every
+ * draw (S, s) with pi = e_1, every right-censored observation c_i of the
+ * context (a unit still in service at age c_i) and every horizon h_j, the
+ * conditional failure probability q = P(T <= c_i + h_j | T > c_i), by
+ * pht_ctx_loglik_unif's evaluator at c_i and at c_i + h_j.  No reference
+ * counterpart.  Limits: pi = e_1, at most 16 horizons, at most 2^22 censored
+ * units per context, mu (c + h) up to roughly 1500 (beyond: the unit is bad
+ * for that draw and horizon, counted and never summed).
+ *
+ * pht_ctx_forecast: ndraws draws as in pht_ctx_loglik_unif, `batch` (1..64)
+ *   per launch; nh (1..16) horizons, each finite, >= 0, strictly increasing.
+ *   words_out: int64 [ndraws][nh][4] = [M, V, nbad, nunits], M and V the sums
+ *   of llrint(q 2^40) and llrint(q (1 - q) 2^40) over the units good for that
+ *   draw and horizon (exact integer sums: shards and ranks add them); a
+ *   flagged draw's words are zero.  qsum_out (double) and cnt_out (int64),
+ *   each [ncens][nh] in the caller's order of the censored observations and
+ *   started from zero by every call: the sum of q over the draws in which the
+ *   unit was good, in draw order, and their number.  q_out: NULL, or
+ *   [ndraws][ncens][nh], NaN where bad (tests and small fleets).
+ *   draw_flags_out (ndraws, may be NULL) as in pht_ctx_loglik_unif.  Refused
+ *   with a message: no censored observation on the context, more than 2^22,
+ *   nh or a horizon outside the above, batch outside 1..64.  The buffers are
+ *   the context's own: its chain and its WAIC state are not affected.
+ * pht_ctx_forecast_units: the number of censored units of the context; with
+ *   idx_out (that many), their indices in the caller's observation order.
+ * pht_ctx_forecast_grid_cap: most blocks of the kernel (0: the default); the
+ *   result does not depend on it.
+ * pht_ctx_forecast_ms: device time of the last call, the table kernel and the
+ *   evaluations.
+ * pht_forecast_host: host only (no GPU), one draw over `ncens` ages; bit for
+ *   bit what the device computes.  ymax_c: the largest censored observation
+ *   the table is sized for (0: the largest of ages).  words_out [nh][4] is
+ *   written; qsum and cnt ([ncens][nh], may be NULL) are UPDATED (one call
+ *   per draw, in order); q_out ([ncens][nh], may be NULL) is written.  Returns
+ *   the draw's flag word, < 0 on error. */
+int pht_ctx_forecast(pht_ctx *c, int ndraws, const double *S, const double *s, int nh, const double *horizons,
+                     int batch, long long *words_out, double *qsum_out, long long *cnt_out, double *q_out,
+                     int *draw_flags_out);
+long pht_ctx_forecast_units(pht_ctx *c, long *idx_out);
+int pht_ctx_forecast_grid_cap(pht_ctx *c, int cap);
+int pht_ctx_forecast_ms(pht_ctx *c, float *table_ms, float *eval_ms);
+int pht_forecast_host(int n, const double *S, const double *s, long ncens, const double *ages, int nh,
+                      const double *horizons, double ymax_c, long long *words_out, double *qsum, long long *cnt,
+                      double *q_out);
+
 /* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
  * the whole definition): per observation, from l[d, i] of every usable draw
  * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail

@@ -30,7 +30,9 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "posterior_predictive", "ppc", "ppc_from_predict", "quantiles_from_counts", "loo", "loo_from_psis",
            "loo_compare", "PSIS_MAX_DRAWS", "estep_contract", "expected_stats", "complete_stats",
            "em_step", "ph_em", "ESTEP_MAX_OBS", "qph", "pph", "dph", "ph_quantiles", "quantile_host",
-           "Q_F_P", "Q_F_T0", "Q_F_BEYOND", "Q_F_EVAL", "Q_F_CAP", "Q_F_DRAW"]
+           "Q_F_P", "Q_F_T0", "Q_F_BEYOND", "Q_F_EVAL", "Q_F_CAP", "Q_F_DRAW",
+           "fleet_forecast", "forecast_combine", "forecast_finalise", "forecast_host", "forecast_moments",
+           "forecast_count_quantiles", "FORECAST_MAX_H", "FORECAST_MAX_UNITS"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -64,6 +66,8 @@ EXPORTS = [
     "pht_estep_words", "pht_estep_yscale", "pht_ctx_estep", "pht_estep_contract", "pht_ctx_estep_grid_cap",
     "pht_ctx_estep_ms",
     "pht_ctx_quantile", "pht_ctx_quantile_ms", "pht_quantile_host",
+    "pht_ctx_forecast", "pht_ctx_forecast_units", "pht_ctx_forecast_grid_cap", "pht_ctx_forecast_ms",
+    "pht_forecast_host",
 ]
 
 
@@ -172,6 +176,14 @@ def load(build_if_needed: bool = True) -> C.CDLL:
                                    _dp, _dp, _ip, _up, _ip]
     L.pht_ctx_quantile_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pht_quantile_host.argtypes = [C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _up]
+    L.pht_ctx_forecast.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _lp, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, _ip]
+    L.pht_ctx_forecast_units.restype = C.c_long
+    L.pht_ctx_forecast_units.argtypes = [C.c_void_p, C.c_void_p]
+    L.pht_ctx_forecast_grid_cap.argtypes = [C.c_void_p, C.c_int]
+    L.pht_ctx_forecast_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_forecast_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -568,6 +580,67 @@ class Sweeper:
         self.L.pht_ctx_quantile_ms(self.ctx, C.byref(tm), C.byref(sm))
         self.last_quantile_ms = (tm.value, sm.value)
         return dict(t=t, lo=lo, hi=hi, nev=nev, flags=flags, bad_draw=dflags != 0, draw_flags=dflags)
+
+    def forecast_units(self) -> np.ndarray:
+        """pht_ctx_forecast_units: the indices, in the order given to
+        ``set_obs``, of this shard's censored observations (the units still in
+        service); ``forecast``'s per-unit rows are in this order."""
+        nc = self.L.pht_ctx_forecast_units(self.ctx, None)
+        if nc < 0:
+            raise _err(self.L)
+        idx = np.zeros(nc, np.int64)
+        if nc and self.L.pht_ctx_forecast_units(self.ctx, idx.ctypes.data) < 0:
+            raise _err(self.L)
+        return idx
+
+    def forecast(self, S_list, s_list, horizons, batch: int = 64, pointwise: bool = False, grid_cap: int = 0):
+        """pht_ctx_forecast: for each draw (S, s), each censored observation
+        c_i of this shard (a unit still in service at age c_i) and each horizon
+        h the conditional failure probability q = P(T <= c_i + h | T > c_i)
+        (include/pht_forecast.h), by ``loglik_unif``'s evaluator (its limits
+        apply: pi = e_1, mu (c + h) up to roughly 1500).  At most 16 horizons,
+        finite, >= 0 and strictly increasing; at most 2^22 censored units.
+
+        Returns ``M`` and ``V`` [draws, H] (floats: the mean and the variance
+        of that draw's Poisson-binomial number of failures within h, summed
+        over the units good for that draw and horizon), ``nbad`` and ``nunits``
+        [draws, H] (units that were bad there — beyond the table or below
+        2^-900, never summed — and good), ``words`` (int64 [draws, H, 4] =
+        [M 2^40, V 2^40, nbad, nunits]: exact integer sums, shards and ranks
+        add them, ``forecast_combine``), ``qsum`` and ``cnt`` [units, H] (the
+        sum of q over the draws in which the unit was good, in draw order, and
+        their number), ``p_unit`` = qsum / cnt (the posterior mean failure
+        probability of each unit; NaN where cnt is 0), ``unit_index`` (the
+        units' indices in the order given to ``set_obs``), ``bad_draw`` and
+        ``flags`` as ``loglik_unif`` gives them (a flagged draw is skipped:
+        words zero, cnt untouched), and with ``pointwise`` ``q`` [draws,
+        units, H] (NaN where bad; for tests and small fleets).  ``grid_cap``:
+        most blocks of the kernel (0: the default); the result does not depend
+        on it.  ``last_forecast_ms`` then holds the device time of the table
+        kernel and of the evaluations."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd, n = S_all.shape[0], self.n
+        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
+            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        h = np.ascontiguousarray(np.atleast_1d(horizons), np.float64).reshape(-1)
+        H = len(h)
+        idx = self.forecast_units()
+        nc = len(idx)
+        words = np.zeros((nd, max(H, 1), 4), np.int64)
+        qsum, cnt = np.zeros((nc, max(H, 1))), np.zeros((nc, max(H, 1)), np.int64)
+        q = np.full((nd, nc, max(H, 1)), np.nan) if pointwise else None
+        flags = np.zeros(nd, np.int32)
+        if self.L.pht_ctx_forecast_grid_cap(self.ctx, int(grid_cap)) != 0:
+            raise _err(self.L)
+        if self.L.pht_ctx_forecast(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), H, h if H else np.zeros(1),
+                                   int(batch), words.reshape(-1), qsum.ctypes.data, cnt.ctypes.data,
+                                   q.ctypes.data if pointwise else None, flags) != 0:
+            raise _err(self.L)
+        tm, em = C.c_float(0), C.c_float(0)
+        self.L.pht_ctx_forecast_ms(self.ctx, C.byref(tm), C.byref(em))
+        self.last_forecast_ms = (tm.value, em.value)
+        return forecast_finalise(words, qsum, cnt, idx, flags, q)
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
                 horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
@@ -1197,6 +1270,161 @@ def ph_quantiles(res, TT_or_T, probs, given: float = 0.0, C_=None, n=None, burn:
     return dict(q=q, band=bands, n_finite=fin.sum(0), n_beyond=((r["flags"] & Q_F_BEYOND) != 0).sum(0),
                 n_flagged=np.isnan(q).sum(0), flags=r["flags"], bad_draw=r["bad_draw"], lo=r["lo"], hi=r["hi"],
                 nev=r["nev"], probs=np.atleast_1d(np.asarray(probs, np.float64)))
+
+
+# ------------------------------------------------------------ fleet forecasts
+# include/pht_forecast.h, phasetype_amd/csrc/pht_forecast.hip (no reference
+# counterpart): which of the units still in service fail within h, and how many
+FORECAST_MAX_H, FORECAST_MAX_UNITS, FORECAST_SCALE = 16, 1 << 22, 2.0 ** 40
+
+
+def forecast_finalise(words, qsum, cnt, unit_index, flags, q=None) -> dict:
+    """``Sweeper.forecast``'s dict from the raw outputs (words int64 [draws, H,
+    4], qsum and cnt [units, H], the units' indices, the draws' flag words)."""
+    words = np.asarray(words, np.int64)
+    qsum, cnt = np.asarray(qsum, np.float64), np.asarray(cnt, np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p_unit = np.where(cnt > 0, qsum / np.maximum(cnt, 1), np.nan)
+    flags = np.asarray(flags, np.int32)
+    out = dict(M=words[:, :, 0] / FORECAST_SCALE, V=words[:, :, 1] / FORECAST_SCALE, nbad=words[:, :, 2].copy(),
+               nunits=words[:, :, 3].copy(), words=words, p_unit=p_unit, qsum=qsum, cnt=cnt,
+               unit_index=np.asarray(unit_index, np.int64), bad_draw=flags != 0, flags=flags)
+    if q is not None:
+        out["q"] = q
+    return out
+
+
+def forecast_host(S, s, ages, horizons, ymax_c: float = 0.0, state=None) -> dict:
+    """pht_forecast_host (host only, no GPU): ``Sweeper.forecast``'s dict for
+    one draw over units of the given ``ages``, with ``q`` [1, units, H]; bit for
+    bit what the device computes.  ``ymax_c``: the largest censored observation
+    the table is sized for (0: the largest age).  ``state``: the dict of the
+    chain's earlier draws, whose ``qsum`` and ``cnt`` this draw continues (its
+    words are not kept)."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    ages = np.ascontiguousarray(np.atleast_1d(ages), np.float64).reshape(-1)
+    h = np.ascontiguousarray(np.atleast_1d(horizons), np.float64).reshape(-1)
+    nc, H = len(ages), len(h)
+    words = np.zeros((1, max(H, 1), 4), np.int64)
+    if state is None:
+        qsum, cnt = np.zeros((nc, max(H, 1))), np.zeros((nc, max(H, 1)), np.int64)
+    else:
+        qsum, cnt = np.array(state["qsum"], np.float64), np.array(state["cnt"], np.int64)
+        if qsum.shape != (nc, H) or cnt.shape != (nc, H):
+            raise ValueError("state does not have this call's units and horizons")
+    q = np.full((1, nc, max(H, 1)), np.nan)
+    f = L.pht_forecast_host(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                            np.ascontiguousarray(s, np.float64).reshape(-1), nc, ages if nc else np.zeros(1), H,
+                            h if H else np.zeros(1), float(ymax_c), words.reshape(-1), qsum.ctypes.data,
+                            cnt.ctypes.data, q.ctypes.data)
+    if f < 0:
+        raise _err(L)
+    return forecast_finalise(words, qsum, cnt, np.arange(nc), np.array([f], np.int32), q)
+
+
+def forecast_combine(a: dict, b: dict) -> dict:
+    """The forecast of two shards' units from the forecasts of each
+    (``Sweeper.forecast`` of the same draws and horizons on each shard): the
+    words add exactly, the per-unit blocks concatenate (``b``'s units after
+    ``a``'s; ``unit_index`` stays each shard's own numbering)."""
+    if a["words"].shape != b["words"].shape or not np.array_equal(a["flags"], b["flags"]):
+        raise ValueError("the two forecasts are not of the same draws and horizons")
+    q = np.concatenate([a["q"], b["q"]], axis=1) if ("q" in a and "q" in b) else None
+    return forecast_finalise(a["words"] + b["words"], np.concatenate([a["qsum"], b["qsum"]]),
+                             np.concatenate([a["cnt"], b["cnt"]]),
+                             np.concatenate([a["unit_index"], b["unit_index"]]), a["flags"], q)
+
+
+def forecast_moments(M, V, use=None) -> dict:
+    """The predictive moments of the number of failures per horizon from the
+    draws' Poisson-binomial moments ``M``, ``V`` [draws, H] (``use``: which
+    [draw, horizon] cells count; default all): ``mean`` = mean_d M_d, ``within``
+    = mean_d V_d, ``between`` = the variance of M_d over the draws (the
+    mixture's own: divided by the number of draws), ``sd`` = sqrt(within +
+    between) by the law of total variance, ``n_used`` draws per horizon."""
+    M, V = np.atleast_2d(np.asarray(M, np.float64)), np.atleast_2d(np.asarray(V, np.float64))
+    use = np.ones(M.shape, bool) if use is None else np.asarray(use, bool)
+    k = use.sum(0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(use, M, 0.0).sum(0) / k
+        within = np.where(use, V, 0.0).sum(0) / k
+        between = np.where(use, (M - mean) ** 2, 0.0).sum(0) / k
+    return dict(mean=mean, within=within, between=between, sd=np.sqrt(within + between), n_used=k)
+
+
+def forecast_count_quantiles(M, V, p, use=None) -> np.ndarray:
+    """Quantiles [len(p), H] of the predictive number of failures per horizon,
+    APPROXIMATED by the equal-weight mixture over the draws of normals matched
+    to each draw's (M_d, V_d): the x with mean_d Phi((x - M_d) / sqrt(V_d)) = p,
+    by bisection (a draw with V_d = 0 is a step at M_d).  Continuous, not
+    rounded to counts; a Poisson-binomial law of few units or of tiny
+    probabilities is skewed and discrete, which a normal is not (DESIGN.md 5i
+    records the difference against the exact law)."""
+    from scipy.special import ndtr
+
+    M, V = np.atleast_2d(np.asarray(M, np.float64)), np.atleast_2d(np.asarray(V, np.float64))
+    use = np.ones(M.shape, bool) if use is None else np.asarray(use, bool)
+    p = np.atleast_1d(np.asarray(p, np.float64))
+    out = np.full((len(p), M.shape[1]), np.nan)
+    for j in range(M.shape[1]):
+        m, sd = M[use[:, j], j], np.sqrt(np.maximum(V[use[:, j], j], 0.0))
+        if not len(m):
+            continue
+
+        def cdf(x):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                z = np.where(sd > 0, (x - m) / np.where(sd > 0, sd, 1.0), np.where(x >= m, np.inf, -np.inf))
+            return float(np.mean(ndtr(z)))
+
+        lo0, hi0 = float(np.min(m - 40.0 * sd)) - 1.0, float(np.max(m + 40.0 * sd)) + 1.0
+        for i, pv in enumerate(p):
+            if not 0.0 < pv < 1.0:
+                continue
+            lo, hi = lo0, hi0
+            for _ in range(200):
+                mid = 0.5 * (lo + hi)
+                if cdf(mid) < pv:
+                    lo = mid
+                else:
+                    hi = mid
+                if hi - lo <= 1e-12 * max(1.0, abs(hi)):
+                    break
+            out[i, j] = hi
+    return out
+
+
+def fleet_forecast(res, x, TT_or_T, horizons, censored, C_=None, n=None, burn: int = 0, thin: int = 1,
+                   device: int = 0, batch: int = 64, collation: str = "C") -> dict:
+    """The forecast of a fleet from a chain (``res`` and ``TT_or_T`` as in
+    ``log_lik``; rows ``burn::thin``): of the units of ``x`` still in service
+    (``censored`` != 0, at age x_i), how many fail within each of ``horizons``,
+    and which.  ``Sweeper.forecast``'s dict plus, per horizon, ``mean`` (the
+    expected number of failures), ``sd`` (the predictive standard deviation by
+    the law of total variance) with its two parts ``within`` = mean_d V_d (the
+    units' own randomness) and ``between`` = var_d M_d (the posterior's),
+    ``n_used`` (the draws that count for that horizon: not flagged and with no
+    bad unit there; ``mean`` is NaN where none does), ``count_quantiles(p)``
+    (``forecast_count_quantiles``: an approximation) and ``ranking`` [H, units]
+    (the units, as rows of ``p_unit``, by decreasing ``p_unit``, NaN last)."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        r = sw.forecast(S_list, s_list, horizons, batch=batch)
+    finally:
+        sw.close()
+    use = (~r["bad_draw"])[:, None] & (r["nbad"] == 0)
+    r.update(forecast_moments(r["M"], r["V"], use))
+    M, V = r["M"], r["V"]
+    r["count_quantiles"] = lambda p: forecast_count_quantiles(M, V, p, use)
+    key = np.where(np.isnan(r["p_unit"]), -np.inf, r["p_unit"])
+    r["ranking"] = np.argsort(-key, axis=0, kind="stable").T
+    r["horizons"] = np.atleast_1d(np.asarray(horizons, np.float64))
+    return r
 
 
 # ------------------------------------------- expected statistics, EM fitting

@@ -16,6 +16,7 @@
  *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
  *   host_estep.cpp     expected sufficient statistics: pht_ctx_estep, pht_estep_contract
  *   host_quantile.cpp  quantiles and residual-life quantiles: pht_ctx_quantile, pht_quantile_host
+ *   host_forecast.cpp  fleet forecasts of the censored units: pht_ctx_forecast, pht_forecast_host
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -172,6 +173,19 @@ struct pht_ctx {
       long chunk_obs = 0;
       std::vector<unsigned char> usable;
     } loo;
+    /* pht_ctx_forecast: the censored units of these observations, listed on
+     * first use (ncens < 0: not yet): their ages in the device (sorted) order,
+     * unit -> the caller's observation index and -> its rank among the
+     * censored observations in the caller's order, the largest age; a call's
+     * state [unit][nh] (qsum, cnt) and one batch's pointwise values */
+    struct Fcast {
+      long ncens = -1;
+      double ymax_c = 0.0;
+      std::vector<long> idx, rank;
+      DevBuf<double> d_age, d_qsum, d_q;
+      DevBuf<int> d_cnt;
+      size_t qsum_cap = 0, cnt_cap = 0, q_cap = 0;
+    } fc;
   } obs;
   DevBuf<unsigned char> d_params;
   DevBuf<unsigned long long> d_stats;
@@ -262,6 +276,18 @@ struct pht_ctx {
   size_t qin_cap = 0, qout_cap = 0, qouti_cap = 0;
   float q_ms[2] = {0.f, 0.f};
   Event q_ev[3];
+  /* pht_ctx_forecast (allocated on first use; its own buffers and events,
+   * never the sampler's or the WAIC state's): a call's horizons and words
+   * [draw][horizon][4]; the units and their state are obs.fc's, the draws and
+   * tables go through d_lluin and d_llutab.  fc_grid_cap: 0 = two blocks a CU
+   * (pht_ctx_forecast_grid_cap); fc_ms: the last call's device time, tables
+   * and evaluations */
+  DevBuf<double> d_fch;
+  DevBuf<unsigned long long> d_fcwords;
+  size_t fch_cap = 0, fcwords_cap = 0;
+  int fc_grid_cap = 0;
+  float fc_ms[2] = {0.f, 0.f};
+  Event fc_ev[3];
 };
 
 namespace pht {
