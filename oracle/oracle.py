@@ -121,6 +121,8 @@ class OracleLib:
         L.orc_gibbs_z.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _dp,
                                   _dp, C.c_long, _ip, _dp, _dp, C.c_int]
         L.orc_rgamma_ctr_v.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_long, _dp]
+        L.orc_rgamma_ctr_at.restype = C.c_double
+        L.orc_rgamma_ctr_at.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_double, C.c_double]
         L.orc_eig.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
         L.orc_eig_refine.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
         L.orc_eig_fallback_count.restype = C.c_long
@@ -236,6 +238,11 @@ class OracleLib:
         out = np.zeros(cnt)
         self.lib.orc_rgamma_ctr_v(key[0], key[1], a, scale, cnt, out)
         return out
+
+    def rgamma_ctr_at(self, key, param, it, a, scale):
+        """The resident chain's Gamma(a, scale) draw of parameter ``param`` at
+        sweep ``it`` (gibbs dev = 2; it = 0: the initial prior draw)."""
+        return float(self.lib.orc_rgamma_ctr_at(key[0], key[1], int(param), int(it), float(a), float(scale)))
 
     def gibbs(self, dev, it, mhit, method, n, nu, zeta, T, C_, y, censored=None, start=None):
         """dev: 0 the reference's algorithm (R stream), 1 the GPU spec (host

@@ -714,6 +714,14 @@ void orc_stream_u(uint32_t k0, uint32_t k1, uint32_t obs, uint32_t tag, uint32_t
   for (long i = 0; i < cnt; i++) out[i] = pht_next_u(&s);
 }
 
+/* the resident chain's Gamma draw of parameter `param` at sweep `iter`
+ * (orc_gibbs_z dev = 2; iter 0 = the initial prior draw) */
+double orc_rgamma_ctr_at(uint32_t k0, uint32_t k1, int param, uint32_t iter, double a, double scale) {
+  pht_stream s;
+  pht_stream_init(&s, k0, k1, PHT_GAMMA_OBS(param), PHT_GAMMA_TAG, iter);
+  return pht_rgamma_ctr(&s, a, scale);
+}
+
 /* probe for tests: n Gamma(a, scale) draws from the counter streams
  * (key k0,k1; parameter index i, sweep i) */
 void orc_rgamma_ctr_v(uint32_t k0, uint32_t k1, double a, double scale, long cnt, double *out) {

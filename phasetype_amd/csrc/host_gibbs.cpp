@@ -26,91 +26,6 @@ extern "C" int pht_zexp(const double *y, long l) {
   return std::min(1000, std::max(-1000, 52 - e));
 }
 
-/* ============================================================ Gibbs core */
-namespace {
-/* The map draw -> generator shared by GibbsState and pht_theta_to_S
- * (src/PHT_MCMC_Aslett.c:214-262, :380-397): cell (i, j) of the (n+1)^2
- * matrix TT with T[i + j n1] = k + 1 holds theta_k C[i + j n1]; the diagonal
- * of a transient row is minus the sum of the row's cells. */
-inline double tt_cell(double theta, double c) { return theta * c; }
-/* row i's diagonal.  reverse = false: cells by increasing column (how the
- * reference initialises the chain); true: by decreasing column, the
- * reverse-insertion order in which its update refreshes every later draw */
-inline double tt_diag(int n1, const int *T, const double *TT, int i, bool reverse) {
-  double tmp = 0.0;
-  for (int q = 0; q < n1; q++) {
-    const int j = reverse ? n1 - 1 - q : q;
-    if (T[i + j * n1] != 0) tmp -= TT[i + j * n1];
-  }
-  return tmp;
-}
-/* (S, s) = the transient block and exit column of TT */
-inline void tt_split(int n, const double *TT, double *S, double *s) {
-  const int n1 = n + 1;
-  for (int i = 0; i < n; i++)
-    for (int j = 0; j < n; j++) S[i + j * n] = TT[i + j * n1];
-  for (int i = 0; i < n; i++) s[i] = TT[i + n * n1];
-}
-
-/* The reference's Gibbs bookkeeping (src/PHT_MCMC_Aslett.c:187-405) with
- * the linked lists kept as arrays visited in list (reverse-insertion)
- * order, so zsum and the diagonal refresh sum in the reference's order. */
-struct GibbsState {
-  int it, n, m, n1;
-  const double *nu, *zeta;
-  const int *T;
-  double *res;
-  std::vector<double> TT, S, s;
-  const std::vector<std::vector<Ent>> &Nl, &Sl, &sl, &zl, &TTl;
-
-  /* L: the lists of (T, C), built by the caller (who reports a bad T) */
-  template <class Rng>
-  GibbsState(Rng &R, int it_, int n_, int m_, const double *nu_, const double *zeta_, const int *T_,
-             const ParamLists &L, const double *start, double *res_)
-      : it(it_), n(n_), m(m_), n1(n_ + 1), nu(nu_), zeta(zeta_), T(T_), res(res_),
-        Nl(L.Nl), Sl(L.Sl), sl(L.sl), zl(L.zl), TTl(L.TTl) {
-    TT.assign(n1 * n1, 0.0);
-    S.assign(n * n, 0.0);
-    s.assign(n, 0.0);
-    if (start[0] < 0) {
-      for (int i = 0; i < m; i++)
-        res[0 + (size_t)i * it] = (nu[i] > 1) ? (nu[i] - 1.0) / zeta[i] : R.gamma(nu[i], 1.0 / zeta[i]);
-    } else {
-      for (int i = 0; i < m; i++) res[0 + (size_t)i * it] = start[i];
-    }
-    for (int k = 0; k < m; k++)
-      for (const Ent &e : TTl[k]) TT[e.i + e.j * n1] = tt_cell(res[0 + (size_t)k * it], e.c);
-    for (int i = 0; i < n1; i++) TT[i + i * n1] = tt_diag(n1, T, TT.data(), i, false);
-    tt_split(n, TT.data(), S.data(), s.data());
-  }
-
-  /* steps 4-5 (:340-397): compile statistics and draw from the posteriors */
-  template <class Rng>
-  void update(Rng &R, int iter, const double *z, const long long *Nt) {
-    std::vector<long long> Nsum(m, 0);
-    std::vector<double> zsum(m, 0.0);
-    for (int k = 0; k < m; k++) {
-      for (int e = (int)Nl[k].size() - 1; e >= 0; e--) Nsum[k] += Nt[Nl[k][e].i + Nl[k][e].j * n];
-      for (int e = (int)zl[k].size() - 1; e >= 0; e--) zsum[k] += z[zl[k][e].i] / zl[k][e].c;
-    }
-    for (int k = 0; k < m; k++) {
-      const double tmp = res[iter + (size_t)k * it] =
-          R.gamma(nu[k] + (double)(int)Nsum[k], 1.0 / (zeta[k] + zsum[k]));
-      for (int e = (int)TTl[k].size() - 1; e >= 0; e--)
-        TT[TTl[k][e].i + TTl[k][e].j * n1] = tt_cell(tmp, TTl[k][e].c);
-      for (int e = (int)Sl[k].size() - 1; e >= 0; e--) S[Sl[k][e].i + Sl[k][e].j * n] = tt_cell(tmp, Sl[k][e].c);
-      for (int e = (int)sl[k].size() - 1; e >= 0; e--) s[sl[k][e].i] = tt_cell(tmp, sl[k][e].c);
-    }
-    for (int i = 0; i < n; i++) { /* Dl[i] in reverse = the row's cells by decreasing column */
-      const double tmp = tt_diag(n1, T, TT.data(), i, true);
-      TT[i + i * n1] = tmp;
-      S[i + i * n] = tmp;
-    }
-  }
-};
-
-}  // namespace
-
 /* Run the Gibbs loop over a set of device shards; reduce = optional
  * cross-process all-reduce of the int64 statistics block. */
 template <class Rng>
@@ -120,7 +35,9 @@ int pht::host::gibbs_run(Rng &R, int it, int method, int n, int m, const double 
                          double *kernel_ms_total) {
   ParamLists L;
   if (L.build(n, m, T, C)) {
-    set_err("Gibbs run: T[%d,%d] = %d outside 0..m", L.bad_i, L.bad_j, L.bad_t);
+    char why[160];
+    L.describe(why, sizeof why);
+    set_err("Gibbs run: %s", why);
     return -1;
   }
   GibbsState G(R, it, n, m, nu, zeta, T, L, start, res);
@@ -357,7 +274,9 @@ extern "C" int pht_theta_to_S(int n, int m, const int *T, const double *C, const
   const int n1 = n + 1;
   ParamLists L;
   if (L.build(n, m, T, C)) {
-    set_err("pht_theta_to_S: T[%d,%d] = %d outside 0..m", L.bad_i, L.bad_j, L.bad_t);
+    char why[160];
+    L.describe(why, sizeof why);
+    set_err("pht_theta_to_S: %s", why);
     return -1;
   }
   std::vector<double> TT((size_t)n1 * n1, 0.0);

@@ -45,7 +45,9 @@ extern "C" int pht_gibbs_run_resident(pht_ctx *c, int it, int method, int m, con
   /* GibbsState's parameter lists (host_lists.h) as CSR, insertion order */
   ParamLists L;
   if (L.build(n, m, T, C)) {
-    set_err("pht_gibbs_run_resident: T[%d,%d] = %d outside 0..m", L.bad_i, L.bad_j, L.bad_t);
+    char why[160];
+    L.describe(why, sizeof why);
+    set_err("pht_gibbs_run_resident: %s", why);
     return -1;
   }
   std::vector<int> ints;   /* nl_off[m+1] nl_idx zl_off[m+1] zl_i tl_off[m+1] tl_ij dl_off[n+1] dl_ij */
