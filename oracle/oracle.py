@@ -10,13 +10,19 @@ The CPU oracle lives under oracle/ and is used only by tests/, bench.py's
   variant: Philox + detmath + fixed-point z, bit-exact with the HIP kernels
   (the GPU specification).
 
-PARITY UNPINNED: the reference's own tests hold no fixtures (its
-tests/*.R only print) and its C needs R's headers and nmath, which this image
-lacks, so it cannot be built or run here.  What checks the restatement
-instead: R's published set.seed outputs for the R stream,
-Random123's known answers for Philox, RNG-free analytic expectations (Van
-Loan), brute-force forward simulation for censored paths, and the committed
-regression vectors of tests/golden/.
+* ``RefLib`` — oracle/_ref/libpht_ref.so, the reference's own C compiled
+  where it lies on an R-API stand-in (oracle/rshim/, oracle/ref_entry.c;
+  ``build_ref()``).  It exists only where the reference's sources do; CPU
+  tests compare the ``ref`` variant with it bit for bit
+  (tests/test_reference_pin.py) and tools/make_golden.py records fixtures
+  from it.  smoke(), bench.py and the GPU tests never load it.
+
+ALGORITHM PINNED, RUNTIME STAND-IN: the reference's C, given
+R's API, equals the ``ref`` variant draw for draw on the matrix of
+tests/test_reference_pin.py.  R's own nmath (rgamma above all, which has no
+published vector) and R's bundled BLAS/LAPACK remain stand-ins: the R stream
+is checked against R's published set.seed outputs, Philox against
+Random123's known answers.
 
 Nothing in phasetype_amd/ imports this module.
 """
@@ -32,6 +38,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 ORC_SO = os.path.join(HERE, "_build", "liboracle.so")
+REF_SO = os.path.join(HERE, "_ref", "libpht_ref.so")
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _ip = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -54,6 +61,22 @@ def lapack_path() -> tuple[str, str]:
 
 def build() -> None:
     subprocess.run(["make", "-s", "-C", HERE, "oracle"], check=True)
+
+
+def ref_src() -> str:
+    """The directory of the reference's C sources: $PHT_REFERENCE_SRC, or
+    ``reference/src`` beside the repository."""
+    return os.environ.get("PHT_REFERENCE_SRC") or os.path.join(os.path.dirname(REPO), "reference", "src")
+
+
+def build_ref() -> bool:
+    """Compile the reference where it lies into oracle/_ref/libpht_ref.so
+    (oracle/Makefile, target ref).  True if the library was built; False,
+    with nothing built and no error, where the reference's sources are
+    absent."""
+    src = ref_src()
+    subprocess.run(["make", "-s", "-C", HERE, "ref", "REFSRC=" + src], check=True)
+    return os.path.isdir(src)
 
 
 def gibbs_argv(it, mhit, method, n, nu, zeta, T, C_, y, censored, start, silent):
@@ -256,3 +279,69 @@ class OracleLib:
         self.lib.orc_gibbs(int(dev), it, mhit, method, n, len(nu), a["nu"], a["zeta"], a["T"], a["C"], a["y"],
                            len(y), a["censored"], a["start"], a["res"])
         return a["res"].reshape(len(nu), it).T.copy()
+
+
+class RefLib:
+    """The reference's own compiled C (oracle/_ref/libpht_ref.so): one R
+    stream (``set_seed``), the LAPACK of ``lapack_path()``."""
+
+    def __init__(self, path: str = REF_SO):
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.lib = L = C.CDLL(path)
+        L.rshim_bind_lapack.argtypes = [C.c_char_p, C.c_char_p]
+        p, pre = lapack_path()
+        if L.rshim_bind_lapack(p.encode(), pre.encode()) != 0:
+            raise RuntimeError("could not bind LAPACK for the reference build")
+        L.rshim_set_seed.argtypes = [C.c_uint32]
+        L.rshim_nword.restype = C.c_ulonglong
+        L.rshim_print_count.restype = C.c_long
+        L.ref_gibbs.argtypes = [_ip, _ip, _ip, _ip, _ip, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _ip, _dp]
+        L.ref_eigen.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
+        L.ref_sweep.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _ip, C.c_int, _dp, _ip, _ip, _u32p]
+
+    def set_seed(self, seed: int) -> None:
+        self.lib.rshim_set_seed(seed & 0xFFFFFFFF)
+
+    def nword(self) -> int:
+        """32-bit MT words drawn since set_seed"""
+        return int(self.lib.rshim_nword())
+
+    def print_count(self) -> int:
+        """Rprintf / REprintf calls since the library was loaded"""
+        return int(self.lib.rshim_print_count())
+
+    def gibbs(self, it, mhit, method, n, nu, zeta, T, C_, y, censored=None, start=None, silent=1):
+        """LJMA_Gibbs: the (it, m) chain, as OracleLib.gibbs(0, ...) lays it out"""
+        if censored is None:
+            censored = np.zeros(len(y), np.int32)
+        if start is None:
+            start = np.array([-1.0])
+        a = gibbs_argv(it, mhit, method, n, nu, zeta, T, C_, y, censored, start, silent)
+        self.lib.ref_gibbs(*(a[k] for k in ("it", "mhit", "method", "n", "m", "nu", "zeta", "T", "C", "y", "l",
+                                              "censored", "start", "silent", "res")))
+        return a["res"].reshape(len(nu), it).T.copy()
+
+    def eigen(self, S):
+        """LJMA_LAPACKspace + LJMA_eigen: (info, evals, Q, Qinv)"""
+        S = np.asarray(S, np.float64)
+        n = S.shape[0]
+        ev, Q, Qi = np.zeros(n), np.zeros(n * n), np.zeros(n * n)
+        info = self.lib.ref_eigen(n, np.ascontiguousarray(S.reshape(-1, order="F")), ev, Q, Qi)
+        return info, ev, Q.reshape(n, n, order="F"), Qi.reshape(n, n, order="F")
+
+    def sweep(self, method, S, s, y, censored=None, mhit=1):
+        """One step 1 at (S, s), per observation, in OracleLib.ref_sweep's
+        layout: B[l], z[l, n], N[l, from, to], nword[l]"""
+        S = np.asarray(S, np.float64)
+        n = S.shape[0]
+        y = np.ascontiguousarray(y, np.float64)
+        l = len(y)
+        cen = np.zeros(l, np.int32) if censored is None else np.ascontiguousarray(censored, np.int32)
+        z, B = np.zeros(l * n), np.zeros(l, np.int32)
+        N, nw = np.zeros(l * n * n, np.int32), np.zeros(l, np.uint32)
+        info = self.lib.ref_sweep(method, n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                                  np.ascontiguousarray(s, np.float64), mhit, y, cen, l, z, B, N, nw)
+        if info < 0:
+            raise ValueError(f"method {method} names no reference sampler")
+        return dict(info=info, B=B, z=z.reshape(l, n), N=N.reshape(l, n, n).transpose(0, 2, 1), nword=nw)

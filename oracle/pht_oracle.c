@@ -647,6 +647,10 @@ void orc_gibbs_z(int dev, int it, int mhit, int method, int n, int m, const doub
   int *Nsum = calloc(m, sizeof(int));
   double *zsum = calloc(m, sizeof(double));
   int disp = dispatch(method);
+  /* UNIF is no method of the reference: to its chain a word with none of its
+   * three sampler bits is unknown (src/PHT_MCMC_Aslett.c:334-337), and the
+   * ref variant follows it instead of reaching orc_ref_sweep's abort */
+  if (!dev && disp == ORC_UNIF) disp = 0;
   for (int iter = 1; iter < it; iter++) {
     if (!disp) continue; /* "CRITICAL ERROR: Unknown sampling method" */
     orc_sp_build(sp, n, S, s,

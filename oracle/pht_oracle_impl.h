@@ -6,14 +6,11 @@
  *
  *   ORC_DEV == 0  "ref" variant: R's random stream, glibc exp/log and the
  *                 reference's own expression/loop order (natural-order
- *                 BLAS): the reference's algorithm draw for draw.  PARITY
- *                 UNPINNED: the reference needs R's headers and nmath,
- *                 absent here, so nothing compiles it; the rounds-1/2
- *                 stand-in build is retired.  The committed regression
- *                 vectors tests/golden/g1-g3 (first written by that build,
- *                 regenerated bit for bit by tools/make_golden.py --check)
- *                 are the only remaining link to the reference's C
- *                 (DESIGN.md §2).
+ *                 BLAS): the reference's algorithm draw for draw.  PINNED
+ *                 to the reference's own C, compiled where it lies on an
+ *                 R-API stand-in (oracle/Makefile, target ref): bit for bit
+ *                 on the matrix of tests/test_reference_pin.py.  R's nmath
+ *                 and BLAS/LAPACK remain stand-ins.
  *   ORC_DEV == 1  "dev" variant: the GPU specification — Philox stream per
  *                 observation (include/pht_philox.h), detmath exp/log
  *                 (include/pht_detmath.h), per-sweep precomputed products

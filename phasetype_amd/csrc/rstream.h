@@ -16,8 +16,10 @@
  *   set.seed(1); rexp(1)   -> 0.7551818
  *   set.seed(1); rnorm(5)  -> -0.6264538 0.1836433 -0.8356286 1.5952808 0.3295078
  * (tests/test_rstream.py).  rgamma has no such published vector available
- * offline: it is "parity unpinned" beyond the shared exp_rand/norm_rand/
- * unif_rand primitives it is built from.
+ * offline: it remains a stand-in for R's own, checked only through the
+ * exp_rand/norm_rand/unif_rand primitives it is built from.  The reference's
+ * compiled C draws through this same stream in tests/test_reference_pin.py,
+ * so that pin covers the reference's algorithm, not R's nmath.
  */
 #ifndef PHT_RSTREAM_H
 #define PHT_RSTREAM_H

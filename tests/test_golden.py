@@ -1,12 +1,13 @@
-"""CPU: the restatement against its committed regression vectors.
+"""CPU: the restatement against its committed vectors.
 
 tests/golden/g1-g3 hold whole chains and per-observation sweeps of the
 restatement's "ref" variant (R stream + libm + the reference's arithmetic
-order; tools/make_golden.py).  They were first written in round 1 by a build
-of the reference against stand-in R headers, which the rules class as
-unbuildable; round 3 regenerated them from the restatement, bit
-for bit.  So they are regression vectors, not pins: parity with the reference
-is unpinned.  Bar: the "ref" variant reproduces them bit for bit.
+order; tools/make_golden.py).  The reference's own C, compiled where it lies
+on an R-API stand-in, reproduces the same files bit for bit
+(tests/test_reference_pin.py, tools/make_golden.py --reference-check), so
+they pin the reference's algorithm given R's API; R's nmath and BLAS/LAPACK
+remain stand-ins.  Bar: the "ref" variant reproduces them bit
+for bit.
 """
 import os
 

@@ -1,8 +1,9 @@
 """CPU: the oracle's two variants against each other and against analytics.
 
-Parity with the reference is UNPINNED: the reference needs R
-and cannot be built here, and its tests hold no fixtures.  The checks that
-stand in for a pin are RNG-free:
+The ref variant is pinned bit for bit to the reference's own compiled C in
+tests/test_reference_pin.py (algorithm pinned, R's runtime a
+stand-in).  The checks here hold the samplers to the laws they target, and
+are RNG-free:
 
 * Van Loan conditional expectations E[z | Y=y], E[N | Y=y] for exact
   observations, and their censored counterparts

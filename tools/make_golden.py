@@ -1,14 +1,27 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz from the CPU restatement's "ref" variant.
+"""Generate tests/golden/*.npz: from the CPU restatement's "ref" variant, and
+from the reference's own compiled C.
 
 ``python tools/make_golden.py``.  The fixtures hold inputs and outputs only.
-They are REGRESSION vectors of the restatement (oracle/, "ref" variant: R's
-stream + libm + the reference's arithmetic order), not pins: the reference
-needs R's headers, nmath and RNG, which this image lacks, so it is unbuildable
-here ("parity unpinned").  G1–G3 were first written in round 1
-by a build of the reference against stand-in R headers; round 3 retired that
-build and regenerates the same files from the restatement, bit for bit
-(``--check`` compares without writing).  Per SURVEY.md §8(c):
+G1–G3 and G5 are written from the restatement (oracle/, "ref" variant: R's
+stream + libm + the reference's arithmetic order; ``--check`` compares without
+writing).  Two modes use the reference binary instead (oracle/_ref/
+libpht_ref.so: the reference's C compiled where it lies on an R-API stand-in,
+oracle.build_ref(); they need the reference's sources):
+
+* ``--reference-check`` regenerates G1–G3 from the reference binary and
+  compares them with the committed files, which it must reproduce bit for
+  bit: the committed vectors are then the reference's as much as the
+  restatement's (tests/test_reference_pin.py makes the same comparison).
+* ``--from-reference`` writes R1 ``r1_reference.npz``: inputs and outputs of a
+  subset of the matrix of tests/reference_pin.py (recorded_subset: chains of
+  bd_exit at n = 3, 10, 20 under every sampler and censoring, every tied and
+  scaled structure of tests/update_cases.py, per-observation sweeps at n = 3
+  and 10), every call in a child process under a time limit.  The test that
+  replays it on the ref variant runs where the reference is absent too.
+
+What the reference binary pins is the reference's C given R's API; R's nmath
+and BLAS/LAPACK are stand-ins.  Per SURVEY.md §8(c):
 
 * G1 ``g1_test_scripts.npz`` — LJMA_Gibbs chains of the reference's two test
   scripts, with the exact .C vectors of SURVEY.md §4.2 (tests/phtMCMC.R:1-22,
@@ -28,7 +41,8 @@ build and regenerates the same files from the restatement, bit for bit
   5/50/95 % quantiles with batch-means MCSEs.
 
 usage: python3 tools/make_golden.py [--check] [g1_test_scripts g2_cfg1 g3_sweeps g5_posterior]
-(no names: all fixtures)
+       python3 tools/make_golden.py --reference-check | --from-reference
+(no names: all fixtures of the restatement)
 """
 import os
 import sys
@@ -171,8 +185,59 @@ def g5(orc):
     return out
 
 
+class RefAsOracle:
+    """oracle.RefLib behind the calls g1-g3 make of oracle.OracleLib"""
+
+    def __init__(self):
+        self.ref = O.RefLib()
+        self.set_seed = self.ref.set_seed
+
+    def gibbs(self, dev, it, mhit, method, n, nu, zeta, T, C_, y, censored=None, start=None):
+        assert dev == 0
+        return self.ref.gibbs(it, mhit, method, n, nu, zeta, T, C_, y, censored, start)
+
+    def ref_sweep(self, method, S, s, y, censored=None, mhit=1):
+        return self.ref.sweep(method, S, s, y, censored, mhit=mhit)
+
+
+def _need_reference():
+    if not O.build_ref():
+        sys.exit(f"the reference's sources are not at {O.ref_src()} (set PHT_REFERENCE_SRC)")
+
+
+def reference_check():
+    _need_reference()
+    ref = RefAsOracle()
+    ok = True
+    for name, fn in (("g1_test_scripts", g1), ("g2_cfg1", g2), ("g3_sweeps", g3)):
+        d, old = fn(ref), np.load(os.path.join(OUT, name + ".npz"))
+        bad = [k for k in d if k not in old or np.asarray(d[k]).tobytes() != old[k].tobytes()]
+        bad += [k for k in old.files if k not in d]
+        print(name, "from the reference binary:", "identical to the committed file" if not bad else f"DIFFERS in {bad}")
+        ok = ok and not bad
+    return ok
+
+
+def from_reference():
+    _need_reference()
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import reference_pin as RP
+
+    side = RP.Side("ref")
+    out = RP.pack_all([(name, job, side.call(job)) for name, job in RP.recorded_subset()])
+    side.close()
+    names = out["names"]
+    path = os.path.join(OUT, "r1_reference.npz")
+    np.savez_compressed(path, **out)
+    print("r1_reference", len(names), "cases,", os.path.getsize(path), "bytes")
+
+
 def main():
     O.build()
+    if "--reference-check" in sys.argv:
+        sys.exit(0 if reference_check() else 1)
+    if "--from-reference" in sys.argv:
+        return from_reference()
     orc = O.OracleLib()
     os.makedirs(OUT, exist_ok=True)
     check = "--check" in sys.argv
