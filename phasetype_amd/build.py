@@ -65,7 +65,7 @@ UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT
     # polynomial take more scalar registers than there are (2 to 17 spilled, and 22 to 31 more VGPRs)
     ("pht_forecast.hip", (), ("-mllvm", "-disable-machine-licm"))] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
+HEADERS = ["pht_claim.h", "pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
            "pht_loglik_args.h", "pht_loglik_unif_args.h", "pht_predict_args.h", "pht_psis_args.h", "pht_estep_args.h",
            "pht_quantile_args.h", "pht_forecast_args.h",

@@ -278,6 +278,13 @@ void pht::host::ecs_claim_knobs(const pht_ctx *c, SweepArgs &ae) {
    * lane (the longest paths, one per wavefront; tools/latency.py:
    * -10 % at 31k-125k per GPU); PHT_SPREAD=0|1 forces it */
   ae.spread = env_int("PHT_SPREAD", c->n_exact <= 2 * kSpreadLanes);
+  /* the share of a CU's older block against its younger one when the grid is
+   * two one-lane blocks per CU (pair_pos, pht_claim.h): PHT_ECS_PAIR=43 | 32
+   * for 4:3 | 3:2, 0 for the equal stripes; the launcher applies it only to
+   * such a grid (no rows, no spread: the large shards).  On where it was
+   * measured to pay (profiles/r14/ab/: kernel -6.9 % at cfg4, -8.4 % at
+   * n = 5, 10^6); n = 15 at 10^6 is flat and n = 20 loses 4.6 %: the stripes */
+  ae.pair = env_int("PHT_ECS_PAIR", (c->n == 5 || c->n == 10) ? 43 : 0);
 }
 
 /* the sweep kernels of one context on its stream(s): ECS exact and censored
@@ -384,6 +391,16 @@ int pht::host::ctx_enqueue(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep,
     a.dbg_flags = g.d_flags.get();
     a.dbg_ndraw = g.d_ndraw.get();
   }
+#ifdef PHT_BLOCK_TIMES
+  /* variant builds: the per-block records, zeroed ahead of the kernel-time
+   * markers (a block that wrote nothing reads as zeros) */
+  {
+    const size_t words = (size_t)kBlkTimeCap * kBlkTimeWords;
+    if (!c->d_blkt) HIPCHK(c->d_blkt.alloc(words));
+    HIPCHK(hipMemsetAsync(c->d_blkt.get(), 0, sizeof(unsigned long long) * words, st));
+    a.blk_times = c->d_blkt.get();
+  }
+#endif
   if (c->method == kMethodUNIF && unif_prepare(c, a)) return -1;
   /* the kernel-time markers: the GPU idles while the host enqueues them
    * (~9 us per sweep at cfg4, profiles/r06/kernel_events/), so the Gibbs loop
@@ -570,6 +587,21 @@ extern "C" int pht_ctx_sweep_debug(pht_ctx *c, const double *S, const double *s,
   return 0;
 }
 
+#ifdef PHT_BLOCK_TIMES
+/* variant builds: the last sweep's per-block records (kBlkTimeWords words
+ * each, pht_kernels.h) into out[cap * words]; returns the records copied */
+extern "C" __attribute__((visibility("default"))) long pht_ctx_block_times(pht_ctx *c, unsigned long long *out,
+                                                                           long cap, int *words) {
+  if (words) *words = kBlkTimeWords;
+  if (!c || !c->d_blkt || cap < 1) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream.get()));
+  const long nrec = std::min<long>(cap, kBlkTimeCap);
+  HIPCHK(hipMemcpy(out, c->d_blkt.get(), sizeof(unsigned long long) * (size_t)nrec * kBlkTimeWords,
+                   hipMemcpyDeviceToHost));
+  return nrec;
+}
+#endif
 extern "C" float pht_ctx_last_kernel_ms(pht_ctx *c) { return c->last_ms; }
 extern "C" long long pht_ctx_flagged_obs(pht_ctx *c) { return c->flagged; }
 extern "C" int pht_ctx_set_global_count(pht_ctx *c, long long total) {

@@ -203,6 +203,11 @@ struct pht_ctx {
     DevBuf<uint32_t> d_ndraw;
     long cap = 0;
   } dbg;
+#ifdef PHT_BLOCK_TIMES
+  /* variant builds: the ECS exact kernel's per-block records of the last
+   * sweep (pht_kernels.h; pht_ctx_block_times), allocated by the first sweep */
+  DevBuf<unsigned long long> d_blkt;
+#endif
   float last_ms = 0.f;
   Event ev0, ev1;
   pht::host::ChainGroup *grp = nullptr; /* pht_gibbs_run_chains: exact ECS launched with the other chains */

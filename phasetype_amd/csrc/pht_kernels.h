@@ -49,6 +49,9 @@ struct SweepArgs {
                                   blocks (both set by the launcher) */
   int nmain;
   int rowprio;                 /* ECS exact: wave priority of the row blocks (s_setprio 0-3) */
+  int pair;                    /* ECS exact: weighted dealing between the two blocks of a CU (pair_pos; 0 = the
+                                  stripes), asked for by the host */
+  int pairh;                   /* ECS exact: half the grid when the launch deals that way (set by the launcher) */
   int dcsbrent;                /* DCS: jump times by Find02's Brent search instead of hob_halley (pht_dcs_round.h) */
   int *dcsb;                   /* DCS: per position the end state (| flag), written by dcs_end_kernel ahead of
                                   the round kernel; nullptr: computed in the round kernel */
@@ -71,7 +74,22 @@ struct SweepArgs {
   int *dbg_N;                  /* [count*n*n] */
   int *dbg_B, *dbg_pre, *dbg_flags;
   uint32_t *dbg_ndraw;
+#ifdef PHT_BLOCK_TIMES
+  /* variant builds only (tools/block_times.py): one record of kBlkTimeWords
+   * words per one-lane block of the ECS exact kernel, [kBlkTimeCap] records;
+   * nullptr: none written */
+  unsigned long long *blk_times;
+#endif
 };
+
+#ifdef PHT_BLOCK_TIMES
+/* a block's record: [0..2] the constant-rate clock after staging, before and
+ * after flush_stats; [3..5] the core-clock counter at the same points; [6]
+ * wave-rounds of the block's wave 0; [7] observations the block completed;
+ * [8] __smid() (XCC << 6 | SE << 4 | CU); [9] blocks of the launch */
+constexpr int kBlkTimeWords = 10;
+constexpr int kBlkTimeCap = 4096;
+#endif
 
 /* the device-resident chain's per-sweep update (pht_resident.hip); all
  * pointers are device memory.  Parameter maps (GibbsState's lists,

@@ -25,6 +25,7 @@
 #include <type_traits>
 #include <mutex>
 
+#include "pht_claim.h"
 #include "pht_device.h"
 #include "pht_ecs_round.h"
 #include "pht_ecs_row.h"
@@ -111,14 +112,7 @@ struct Sink {
 template <int NT>
 __device__ __forceinline__ int nval(int n) { return NT > 0 ? NT : n; }
 
-/* Position of a block's t-th claim in the persistent kernels: chunks of
- * kClaimChunk consecutive positions, block b taking chunks b, b + grid, ...
- * (the sorted order is walked by all blocks together; a wavefront's claims
- * are contiguous, so its y/gid loads coalesce).  Increasing in t. */
-constexpr int kClaimChunk = 64;
-__device__ __forceinline__ long claim_pos(long t, unsigned blk, unsigned nblk) {
-  return ((t / kClaimChunk) * (long)nblk + blk) * kClaimChunk + (t % kClaimChunk);
-}
+/* (claim_pos, pair_pos: pht_claim.h) */
 __device__ __forceinline__ long claim_pos(long t) { return claim_pos(t, blockIdx.x, gridDim.x); }
 
 /* ================================================================ MHRS */
@@ -795,6 +789,20 @@ __device__ __forceinline__ void ecs_exact_body(const SweepArgs &a, unsigned blk,
   for (int k = threadIdx.x; k < n + n * n; k += blockDim.x) Bc[k] = 0u;
   if (threadIdx.x == 0) *cursor = 0;
   __syncthreads();
+#ifdef PHT_BLOCK_TIMES
+  /* diagnostic builds: the block's record (pht_kernels.h), written by its
+   * lane 0 with plain stores; the start stamps go out at once, so that no
+   * register carries them through the rounds */
+  unsigned long long *btr =
+      (a.blk_times != nullptr && blk < (unsigned)kBlkTimeCap) ? a.blk_times + (size_t)blk * kBlkTimeWords : nullptr;
+  unsigned bt_rounds = 0;
+  if (threadIdx.x == 0 && btr != nullptr) {
+    btr[0] = wall_clock64();
+    btr[3] = __builtin_amdgcn_s_memtime();
+    btr[8] = (unsigned long long)__smid();
+    btr[9] = (unsigned long long)nblk;
+  }
+#endif
 
   Par<NT> P;
   P.d = (const PHT_LDS double *)lsm;
@@ -830,6 +838,8 @@ __device__ __forceinline__ void ecs_exact_body(const SweepArgs &a, unsigned blk,
      * wavefront instead of 64 to wavefront 0 */
     if (a.spread && t < kBlock)
       return (long)(t & 63) * ((long)nblk * (kBlock / 64)) + (long)(t >> 6) * nblk + blk;
+    /* two blocks per CU: the CU's older block takes the larger share */
+    if (a.pairh > 0) return pair_claim(a.pair, (unsigned)t, blk, (unsigned)a.pairh);
     return claim_pos(t, blk, nblk);
   };
   long nextp = claim();
@@ -956,6 +966,9 @@ __device__ __forceinline__ void ecs_exact_body(const SweepArgs &a, unsigned blk,
 #ifdef PHT_STAMPS
     ln.st_rounds++;
 #endif
+#ifdef PHT_BLOCK_TIMES
+    bt_rounds++;
+#endif
 #ifdef PHT_ECS_DIAG
     /* diagnostic builds: lane-rounds in the general ARMS code (envelope
      * beyond kRoundCap), wave-rounds with at least one such lane, wave-rounds,
@@ -1025,7 +1038,28 @@ __device__ __forceinline__ void ecs_exact_body(const SweepArgs &a, unsigned blk,
   lds_add(&xc[5], (unsigned long long)c_w13);
 #endif
   __syncthreads();
+#ifdef PHT_BLOCK_TIMES
+  /* end of work: every wave of the block has left its rounds */
+  if (threadIdx.x == 0 && btr != nullptr) {
+    btr[1] = wall_clock64();
+    btr[4] = __builtin_amdgcn_s_memtime();
+    btr[6] = (unsigned long long)bt_rounds;
+    btr[7] = xc[0]; /* kXObs (rounds in a PHT_STAMPS build) */
+  }
+#endif
   flush_stats(a.stats, zq, Bc, Nc, xc, n);
+#ifdef PHT_BLOCK_TIMES
+  /* end of flush: every wave's atomics have been acknowledged by the L2 (the
+   * release fence waits for them), so the stamp includes the same-address
+   * drain as far as this block sees it */
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0 && btr != nullptr) {
+    btr[2] = wall_clock64();
+    btr[5] = __builtin_amdgcn_s_memtime();
+  }
+#endif
 }
 
 /*
@@ -1265,6 +1299,10 @@ static hipError_t launch_ecs_exact(const SweepArgs &a, hipStream_t st) {
   if (grid > want) grid = want;
   if (grid < 0) grid = 0;
   b.nmain = (int)grid;
+  /* the weighted dealing (pair_pos) only where its premise holds: one-lane
+   * blocks alone, exactly two of them resident on every CU (blocks b and
+   * b + grid / 2 then share one), the stripes walked in order */
+  b.pairh = (pair_mode_ok(a.pair) && b.rowblk == 0 && !a.spread && bpc == 2 && grid == slots) ? (int)(grid / 2) : 0;
   if (grid + b.rowblk < 1) return hipSuccess;
   if (rows)
     hipLaunchKernelGGL((ecs_exact_kernel<NT, DEBUG, row_ok<NT>()>), dim3((unsigned)(grid + b.rowblk)), dim3(kBlock), sm,

@@ -5,7 +5,12 @@ blocks of 256 persistent lanes (rounds per observation ~ 1 + 2.33 y), each
 block's finish = its busiest lane.  Compares the static stripes
 (claim_pos), boustrophedon stripes, LPT over chunks and a per-stripe greedy
 assignment.  (r06: the model's 12.5 % block imbalance did not show on the
-GPU, profiles/r06/claim_order/.)"""
+GPU, profiles/r06/claim_order/.  r14, tools/block_times.py: the model's
+premise, equal speed for every block, does not hold.  The two blocks of a CU
+run at 25.7 k and 34.9 k cycles per round, the older one first, and the end
+times follow the speed, r = 0.97, not the rounds, r = -0.52; per CU, which
+the model does not see, the late block's end spreads 882-1,000 us.  The
+kernel deals 4 : 3 between the two since then, pht_claim.h.)"""
 import os
 import sys, heapq, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
