@@ -320,6 +320,58 @@ int pht_forecast_host(int n, const double *S, const double *s, long ncens, const
                       const double *horizons, double ymax_c, long long *words_out, double *qsum, long long *cnt,
                       double *q_out);
 
+/* Fleet condition (include/pht_condition.h is the whole definition): for every
+ * draw (S, s) with pi = e_1 and every right-censored observation c_i of the
+ * context (a unit still in service at age c_i), the posterior law phi of the
+ * PHASE the unit is in given that it has survived to c_i, its mean residual
+ * life MRL = phi . (-S)^-1 1 and, per horizon h_j, the expected number of
+ * failures D = phi . r_h when every failed unit is replaced by a new one.  No
+ * reference counterpart.  Limits: pi = e_1, 0 to 16 horizons with mu h up to
+ * roughly 1450, at most 2^22 censored units per context, mu c up to roughly
+ * 1500 (beyond: the unit is bad for that draw, counted and never summed).
+ *
+ * pht_ctx_condition: ndraws draws as in pht_ctx_loglik_unif, `batch` (1..64)
+ *   per launch; nh (0..16) horizons as in pht_ctx_forecast.  words_out: int64
+ *   [ndraws][n + nh + 3] = [Phi_0 .. Phi_{n-1}, L, Delta_0 .. Delta_{nh-1},
+ *   nbad, nunits], the sums over the units good for that draw of
+ *   llrint(phi_j 2^40), llrint((MRL / mscale) 2^40) and
+ *   llrint((D_j / dscale_j) 2^40) (exact integer sums: shards and ranks add
+ *   them); scales_out: [ndraws][1 + nh] = [mscale, dscale_j], powers of two
+ *   that depend on the draw alone; both zero for a flagged draw.  phisum_out
+ *   [ncens][n], mrlsum_out [ncens], dsum_out [ncens][nh] (double) and cnt_out
+ *   [ncens] (int64), in the caller's order of the censored observations and
+ *   started from zero by every call: the sums over the draws in which the unit
+ *   was good, in draw order, and their number.  phi_out: NULL, or
+ *   [ndraws][ncens][n], with mrl_out [ndraws][ncens] and d_out
+ *   [ndraws][ncens][nh] (each NULL or given), NaN where bad (tests and small
+ *   fleets).  draw_flags_out (ndraws, may be NULL): pht_ctx_loglik_unif's flag
+ *   words and 64 (a state that cannot reach absorption), 128 (mu h_max beyond
+ *   the renewal table); a flagged draw is skipped.  Refused with a message: no
+ *   censored observation on the context, more than 2^22, nh or a horizon
+ *   outside the above, batch outside 1..64.  The buffers are the context's
+ *   own: its chain, its WAIC state and its forecast state are not affected.
+ * pht_ctx_condition_grid_cap: most blocks of the unit kernel (0: the default);
+ *   the result does not depend on it.
+ * pht_ctx_condition_ms: device time of the last call, the table kernels and
+ *   the unit kernel.
+ * pht_condition_host: host only (no GPU), one draw over `ncens` ages; bit for
+ *   bit what the device computes.  ymax_c: the largest censored observation
+ *   the tables are sized for (0: the largest of ages).  words_out
+ *   [n + nh + 3] and scales_out [1 + nh] are written; phisum, mrlsum, dsum and
+ *   cnt (may be NULL) are UPDATED (one call per draw, in order); phi_out,
+ *   mrl_out, d_out (may be NULL) are written.  Returns the draw's flag word,
+ *   < 0 on error. */
+int pht_ctx_condition(pht_ctx *c, int ndraws, const double *S, const double *s, int nh, const double *horizons,
+                      int batch, long long *words_out, double *scales_out, double *phisum_out, double *mrlsum_out,
+                      double *dsum_out, long long *cnt_out, double *phi_out, double *mrl_out, double *d_out,
+                      int *draw_flags_out);
+int pht_ctx_condition_grid_cap(pht_ctx *c, int cap);
+int pht_ctx_condition_ms(pht_ctx *c, float *table_ms, float *unit_ms);
+int pht_condition_host(int n, const double *S, const double *s, long ncens, const double *ages, int nh,
+                       const double *horizons, double ymax_c, long long *words_out, double *scales_out,
+                       double *phisum, double *mrlsum, double *dsum, long long *cnt, double *phi_out, double *mrl_out,
+                       double *d_out);
+
 /* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
  * the whole definition): per observation, from l[d, i] of every usable draw
  * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail

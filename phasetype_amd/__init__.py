@@ -32,7 +32,9 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "em_step", "ph_em", "ESTEP_MAX_OBS", "qph", "pph", "dph", "ph_quantiles", "quantile_host",
            "Q_F_P", "Q_F_T0", "Q_F_BEYOND", "Q_F_EVAL", "Q_F_CAP", "Q_F_DRAW",
            "fleet_forecast", "forecast_combine", "forecast_finalise", "forecast_host", "forecast_moments",
-           "forecast_count_quantiles", "FORECAST_MAX_H", "FORECAST_MAX_UNITS"]
+           "forecast_count_quantiles", "FORECAST_MAX_H", "FORECAST_MAX_UNITS",
+           "fleet_condition", "condition_combine", "condition_finalise", "condition_host", "ph_state", "ph_mrl",
+           "CONDITION_MAX_H", "CONDITION_MAX_UNITS", "CD_F_TRAP", "CD_F_HCAP"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -68,6 +70,7 @@ EXPORTS = [
     "pht_ctx_quantile", "pht_ctx_quantile_ms", "pht_quantile_host",
     "pht_ctx_forecast", "pht_ctx_forecast_units", "pht_ctx_forecast_grid_cap", "pht_ctx_forecast_ms",
     "pht_forecast_host",
+    "pht_ctx_condition", "pht_ctx_condition_grid_cap", "pht_ctx_condition_ms", "pht_condition_host",
 ]
 
 
@@ -184,6 +187,12 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_forecast_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pht_forecast_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
+    L.pht_ctx_condition.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _lp, _dp] + \
+        [C.c_void_p] * 7 + [_ip]
+    L.pht_ctx_condition_grid_cap.argtypes = [C.c_void_p, C.c_int]
+    L.pht_ctx_condition_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_condition_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, _dp] + \
+        [C.c_void_p] * 7
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -641,6 +650,64 @@ class Sweeper:
         self.L.pht_ctx_forecast_ms(self.ctx, C.byref(tm), C.byref(em))
         self.last_forecast_ms = (tm.value, em.value)
         return forecast_finalise(words, qsum, cnt, idx, flags, q)
+
+    def condition(self, S_list, s_list, horizons=None, batch: int = 64, pointwise: bool = False, grid_cap: int = 0):
+        """pht_ctx_condition: for each draw (S, s) and each censored observation
+        c_i of this shard (a unit still in service at age c_i) the posterior law
+        phi of the PHASE the unit is in given that it has survived to c_i, its
+        mean residual life MRL = phi . (-S)^-1 1 and, for each of ``horizons``
+        (none, or up to 16 as in ``forecast``), the expected number of failures
+        D within h when every failed unit is replaced by a new one
+        (include/pht_condition.h; ``loglik_unif``'s limits apply: pi = e_1, mu c
+        up to roughly 1500, and mu h up to roughly 1450).
+
+        Returns ``Phi`` [draws, n] (the expected number of units in each phase),
+        ``L`` [draws] (the fleet's total mean residual life), ``Delta`` [draws,
+        H] (the expected failures of the fleet with replacement), ``nbad`` and
+        ``nunits`` [draws] (units that were bad for the draw, never summed, and
+        good), ``words`` (int64 [draws, n + H + 3]: exact integer sums, shards
+        and ranks add them, ``condition_combine``) with ``scales`` [draws, 1 +
+        H] (the powers of two L and Delta are scaled by; they depend on the
+        draw alone), ``phisum`` [units, n], ``mrlsum`` [units], ``dsum`` [units,
+        H] and ``cnt`` [units] (the sums over the draws in which the unit was
+        good, in draw order, and their number), ``p_phase``, ``mrl_unit``,
+        ``demand_unit`` (those sums over cnt: the posterior means; NaN where cnt
+        is 0), ``unit_index``, ``bad_draw`` and ``flags`` (``loglik_unif``'s
+        flag words, ``CD_F_TRAP`` = 64: a state that cannot reach absorption,
+        ``CD_F_HCAP`` = 128: mu h_max beyond the renewal table; a flagged draw is
+        skipped), and with ``pointwise`` ``phi`` [draws, units, n], ``mrl``
+        [draws, units] and ``d`` [draws, units, H] (NaN where bad; for tests and
+        small fleets).  D is a mean: the variance of the replacement count
+        within a draw is not computed.  ``last_condition_ms`` then holds the
+        device time of the table kernels and of the unit kernel."""
+        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+        nd, n = S_all.shape[0], self.n
+        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
+            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        h = np.ascontiguousarray(np.atleast_1d([] if horizons is None else horizons), np.float64).reshape(-1)
+        H = len(h)
+        idx = self.forecast_units()
+        nc = len(idx)
+        words, scales = np.zeros((nd, n + H + 3), np.int64), np.zeros((nd, 1 + H))
+        phisum, mrlsum, dsum = np.zeros((nc, n)), np.zeros(nc), np.zeros((nc, H))
+        cnt = np.zeros(nc, np.int64)
+        phi = np.full((nd, nc, n), np.nan) if pointwise else None
+        mrl = np.full((nd, nc), np.nan) if pointwise else None
+        d = np.full((nd, nc, H), np.nan) if pointwise else None
+        flags = np.zeros(nd, np.int32)
+        if self.L.pht_ctx_condition_grid_cap(self.ctx, int(grid_cap)) != 0:
+            raise _err(self.L)
+        if self.L.pht_ctx_condition(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), H, h if H else np.zeros(1),
+                                    int(batch), words.reshape(-1), scales.reshape(-1), phisum.ctypes.data,
+                                    mrlsum.ctypes.data, dsum.ctypes.data if H else None, cnt.ctypes.data,
+                                    phi.ctypes.data if pointwise else None, mrl.ctypes.data if pointwise else None,
+                                    d.ctypes.data if pointwise and H else None, flags) != 0:
+            raise _err(self.L)
+        tm, um = C.c_float(0), C.c_float(0)
+        self.L.pht_ctx_condition_ms(self.ctx, C.byref(tm), C.byref(um))
+        self.last_condition_ms = (tm.value, um.value)
+        return condition_finalise(words, scales, phisum, mrlsum, dsum, cnt, idx, flags, phi, mrl, d)
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
                 horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
@@ -1425,6 +1492,169 @@ def fleet_forecast(res, x, TT_or_T, horizons, censored, C_=None, n=None, burn: i
     r["ranking"] = np.argsort(-key, axis=0, kind="stable").T
     r["horizons"] = np.atleast_1d(np.asarray(horizons, np.float64))
     return r
+
+
+# ------------------------------------------------------------ fleet condition
+# include/pht_condition.h, phasetype_amd/csrc/pht_condition.hip (no reference
+# counterpart): which phase each unit still in service is in, its mean residual
+# life, and the spares the fleet needs when failed units are replaced
+CONDITION_MAX_H, CONDITION_MAX_UNITS, CONDITION_SCALE = 16, 1 << 22, 2.0 ** 40
+CD_F_TRAP, CD_F_HCAP = 64, 128
+
+
+def condition_finalise(words, scales, phisum, mrlsum, dsum, cnt, unit_index, flags, phi=None, mrl=None,
+                       d=None) -> dict:
+    """``Sweeper.condition``'s dict from the raw outputs (words int64 [draws,
+    n + H + 3], scales [draws, 1 + H], phisum [units, n], mrlsum [units], dsum
+    [units, H], cnt [units], the units' indices, the draws' flag words)."""
+    words = np.asarray(words, np.int64)
+    scales = np.asarray(scales, np.float64)
+    phisum, mrlsum = np.asarray(phisum, np.float64), np.asarray(mrlsum, np.float64)
+    dsum, cnt = np.asarray(dsum, np.float64), np.asarray(cnt, np.int64)
+    n, H = phisum.shape[1], dsum.shape[1]
+    k = np.maximum(cnt, 1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p_phase = np.where(cnt[:, None] > 0, phisum / k[:, None], np.nan)
+        mrl_unit = np.where(cnt > 0, mrlsum / k, np.nan)
+        demand_unit = np.where(cnt[:, None] > 0, dsum / k[:, None], np.nan)
+    flags = np.asarray(flags, np.int32)
+    out = dict(Phi=words[:, :n] / CONDITION_SCALE, L=(words[:, n] / CONDITION_SCALE) * scales[:, 0],
+               Delta=(words[:, n + 1:n + 1 + H] / CONDITION_SCALE) * scales[:, 1:], nbad=words[:, n + H + 1].copy(),
+               nunits=words[:, n + H + 2].copy(), words=words, scales=scales, phisum=phisum, mrlsum=mrlsum,
+               dsum=dsum, cnt=cnt, p_phase=p_phase, mrl_unit=mrl_unit, demand_unit=demand_unit,
+               unit_index=np.asarray(unit_index, np.int64), bad_draw=flags != 0, flags=flags)
+    if phi is not None:
+        out.update(phi=phi, mrl=mrl, d=d)
+    return out
+
+
+def condition_host(S, s, ages, horizons=None, ymax_c: float = 0.0, state=None) -> dict:
+    """pht_condition_host (host only, no GPU): ``Sweeper.condition``'s dict for
+    one draw over units of the given ``ages``, with the pointwise values; bit
+    for bit what the device computes.  ``ymax_c``: the largest censored
+    observation the tables are sized for (0: the largest age).  ``state``: the
+    dict of the chain's earlier draws, whose per-unit sums and ``cnt`` this draw
+    continues (its words are not kept)."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    ages = np.ascontiguousarray(np.atleast_1d(ages), np.float64).reshape(-1)
+    h = np.ascontiguousarray(np.atleast_1d([] if horizons is None else horizons), np.float64).reshape(-1)
+    nc, H = len(ages), len(h)
+    words, scales = np.zeros((1, n + H + 3), np.int64), np.zeros((1, 1 + H))
+    if state is None:
+        phisum, mrlsum, dsum, cnt = np.zeros((nc, n)), np.zeros(nc), np.zeros((nc, H)), np.zeros(nc, np.int64)
+    else:
+        phisum, mrlsum = np.array(state["phisum"], np.float64), np.array(state["mrlsum"], np.float64)
+        dsum, cnt = np.array(state["dsum"], np.float64), np.array(state["cnt"], np.int64)
+        if phisum.shape != (nc, n) or mrlsum.shape != (nc,) or dsum.shape != (nc, H) or cnt.shape != (nc,):
+            raise ValueError("state does not have this call's units, states and horizons")
+    phi, mrl, d = np.full((1, nc, n), np.nan), np.full((1, nc), np.nan), np.full((1, nc, H), np.nan)
+    f = L.pht_condition_host(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                             np.ascontiguousarray(s, np.float64).reshape(-1), nc, ages if nc else np.zeros(1), H,
+                             h if H else np.zeros(1), float(ymax_c), words.reshape(-1), scales.reshape(-1),
+                             phisum.ctypes.data, mrlsum.ctypes.data, dsum.ctypes.data if H else None,
+                             cnt.ctypes.data, phi.ctypes.data, mrl.ctypes.data, d.ctypes.data if H else None)
+    if f < 0:
+        raise _err(L)
+    return condition_finalise(words, scales, phisum, mrlsum, dsum, cnt, np.arange(nc), np.array([f], np.int32), phi,
+                              mrl, d)
+
+
+def condition_combine(a: dict, b: dict) -> dict:
+    """The condition of two shards' units from the conditions of each
+    (``Sweeper.condition`` of the same draws and horizons on each shard): the
+    words add exactly (the scales depend on the draws alone), the per-unit
+    blocks concatenate (``b``'s units after ``a``'s; ``unit_index`` stays each
+    shard's own numbering)."""
+    if a["words"].shape != b["words"].shape or not np.array_equal(a["flags"], b["flags"]) \
+            or not np.array_equal(a["scales"], b["scales"]):
+        raise ValueError("the two conditions are not of the same draws and horizons")
+    pw = [np.concatenate([a[k], b[k]], axis=1) for k in ("phi", "mrl", "d")] if ("phi" in a and "phi" in b) \
+        else [None] * 3
+    return condition_finalise(a["words"] + b["words"], a["scales"], np.concatenate([a["phisum"], b["phisum"]]),
+                              np.concatenate([a["mrlsum"], b["mrlsum"]]), np.concatenate([a["dsum"], b["dsum"]]),
+                              np.concatenate([a["cnt"], b["cnt"]]),
+                              np.concatenate([a["unit_index"], b["unit_index"]]), a["flags"], *pw)
+
+
+def _draw_summary(x, use, band):
+    """posterior mean, sd and quantiles over the rows of x [draws, ...] that count"""
+    x = np.asarray(x, np.float64)
+    sel = x[use]
+    if not len(sel):
+        nan = np.full(x.shape[1:], np.nan)
+        return dict(mean=nan, sd=nan, band=np.full((len(band),) + x.shape[1:], np.nan))
+    return dict(mean=sel.mean(0), sd=sel.std(0), band=np.quantile(sel, band, axis=0))
+
+
+def fleet_condition(res, x, TT_or_T, censored, horizons=None, C_=None, n=None, burn: int = 0, thin: int = 1,
+                    device: int = 0, batch: int = 64, collation: str = "C", band=(.025, .5, .975)) -> dict:
+    """The condition of a fleet from a chain (``res`` and ``TT_or_T`` as in
+    ``log_lik``; rows ``burn::thin``), for the units of ``x`` still in service
+    (``censored`` != 0, at age x_i).  ``Sweeper.condition``'s dict, of which per
+    unit ``p_phase`` [units, n] (the posterior law of the unit's phase: in a
+    Coxian or birth-death structure, its wear stage), ``mrl_unit`` (its
+    posterior mean residual life) and ``demand_unit`` [units, H] (its expected
+    failures within each horizon when replaced at failure), plus ``stage``
+    (argmax of p_phase, -1 where it is NaN) and, per draw and summarised over
+    the ``n_used`` draws that are not flagged and have no bad unit, ``phase``
+    (= Phi [draws, n], the fleet's composition), ``residual_life`` (= L, the
+    fleet's total mean residual life) and ``demand`` (= Delta [draws, H], the
+    spares needed with replacement), each with ``*_mean``, ``*_sd`` and
+    ``*_band`` (the posterior ``band`` quantiles).  The demand of a draw is the
+    MEAN of its replacement count: the variance of the count within a draw is
+    not computed, so ``demand_sd`` is the spread between the draws only, a
+    LOWER bound of the predictive sd."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        r = sw.condition(S_list, s_list, horizons, batch=batch)
+    finally:
+        sw.close()
+    use = (~r["bad_draw"]) & (r["nbad"] == 0)
+    r["use"], r["n_used"] = use, int(use.sum())
+    with np.errstate(invalid="ignore"):
+        r["stage"] = np.where(np.isnan(r["p_phase"]).any(1), -1, np.argmax(np.nan_to_num(r["p_phase"]), axis=1))
+    for key, val in (("phase", r["Phi"]), ("residual_life", r["L"]), ("demand", r["Delta"])):
+        sm = _draw_summary(val, use, band)
+        r[key] = val
+        r[key + "_mean"], r[key + "_sd"], r[key + "_band"] = sm["mean"], sm["sd"], sm["band"]
+    r["horizons"] = np.atleast_1d(np.asarray([] if horizons is None else horizons, np.float64))
+    return r
+
+
+def _condition_one(S, s, t, horizons, device):
+    S = np.asarray(S, np.float64)
+    t = np.asarray(t, np.float64)
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        sw.set_obs(t.reshape(-1), np.ones(t.size, np.int32))
+        r = sw.condition([S], [s], horizons, pointwise=True)
+    finally:
+        sw.close()
+    if r["bad_draw"][0]:
+        raise ValueError(f"not a usable generator (flag {r['flags'][0]})")
+    return r, t
+
+
+def ph_state(S, s, t, device: int = 0):
+    """The law of the phase of PH(e_1, S) at ``t`` given survival to t:
+    e_1 exp(S t) / (e_1 exp(S t) 1), [..., n] for a ``t`` of any shape
+    (``Sweeper.condition`` on one draw; NaN beyond the evaluator's range)."""
+    r, t = _condition_one(S, s, t, None, device)
+    return r["phi"][0].reshape(t.shape + (r["phi"].shape[2],))
+
+
+def ph_mrl(S, s, given=0.0, device: int = 0):
+    """The mean residual life of PH(e_1, S) at age ``given`` (0: the mean):
+    E[T - t | T > t], the shape of ``given``."""
+    r, t = _condition_one(S, s, given, None, device)
+    m = r["mrl"][0].reshape(t.shape)
+    return float(m) if t.ndim == 0 else m
 
 
 # ------------------------------------------- expected statistics, EM fitting

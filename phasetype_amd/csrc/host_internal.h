@@ -17,6 +17,7 @@
  *   host_estep.cpp     expected sufficient statistics: pht_ctx_estep, pht_estep_contract
  *   host_quantile.cpp  quantiles and residual-life quantiles: pht_ctx_quantile, pht_quantile_host
  *   host_forecast.cpp  fleet forecasts of the censored units: pht_ctx_forecast, pht_forecast_host
+ *   host_condition.cpp fleet condition of the censored units: pht_ctx_condition, pht_condition_host
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -293,6 +294,20 @@ struct pht_ctx {
   int fc_grid_cap = 0;
   float fc_ms[2] = {0.f, 0.f};
   Event fc_ev[3];
+  /* pht_ctx_condition (allocated on first use; its own buffers and events,
+   * never the sampler's, the WAIC state's or the forecast's): one batch's
+   * forward tables [draw][k][n], a call's vectors [draw][m, r, scales] and
+   * words [draw][n + nh + 3], the units' sums [unit][n + 2 + nh] and one
+   * batch's pointwise values [unit][draw][n + 1 + nh]; the units are obs.fc's
+   * (read only), the draws and (ax, ac) tables go through d_lluin and
+   * d_llutab.  cd_grid_cap: 0 = two blocks a CU (pht_ctx_condition_grid_cap);
+   * cd_ms: the last call's device time, tables and units */
+  DevBuf<double> d_cdF, d_cdvec, d_cdstate, d_cdpw;
+  DevBuf<unsigned long long> d_cdwords;
+  size_t cdF_cap = 0, cdvec_cap = 0, cdstate_cap = 0, cdpw_cap = 0, cdwords_cap = 0;
+  int cd_grid_cap = 0;
+  float cd_ms[2] = {0.f, 0.f};
+  Event cd_ev[3];
 };
 
 namespace pht {
