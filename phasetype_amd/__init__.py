@@ -204,6 +204,32 @@ def _err(L) -> PhaseTypeError:
     return PhaseTypeError(L.pht_last_error().decode() or "unknown error")
 
 
+def _pack_draws(S_list, s_list, n: int):
+    """(S_all [draws, n n] column-major, s_all [draws, n], draws) of draws (S, s)."""
+    S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
+    s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
+    nd = S_all.shape[0]
+    if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
+        raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+    return S_all, s_all, nd
+
+
+def _totals_dict(tot, bad_draw, **more) -> dict:
+    """loglik_blocks' dict from the int64 totals [draws, 4] = [H, F, nbad, nobs]."""
+    tot = tot.reshape(-1, 4)
+    out = dict(H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(),
+               bad_draw=bad_draw, **more)
+    out["total"] = loglik_total(out["H"], out["F"], out["nbad"], bad_draw)
+    return out
+
+
+def _ms_pair(read, ctx) -> tuple:
+    """The two device times of a pht_ctx_X_ms entry point."""
+    a, b = C.c_float(0), C.c_float(0)
+    read(ctx, C.byref(a), C.byref(b))
+    return (a.value, b.value)
+
+
 def set_seed(seed: int) -> None:
     """R's set.seed() for the standalone host stream (inside R, R's own)."""
     load().pht_set_seed(int(seed) & 0xFFFFFFFF)
@@ -403,11 +429,7 @@ class Sweeper:
         if self.L.pht_ctx_loglik(self.ctx, nd, blocks.ctypes.data, int(batch), tot,
                                  pw.ctypes.data if pointwise else None, int(bool(accumulate))) != 0:
             raise _err(self.L)
-        tot = tot.reshape(nd, 4)
-        bad_draw = blocks[:, :8].copy().view(np.uint64).reshape(nd) != 0
-        out = dict(H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(),
-                   bad_draw=bad_draw)
-        out["total"] = loglik_total(out["H"], out["F"], out["nbad"], bad_draw)
+        out = _totals_dict(tot, blocks[:, :8].copy().view(np.uint64).reshape(nd) != 0)
         if pointwise:
             out["pointwise"] = pw
         return out
@@ -422,22 +444,14 @@ class Sweeper:
         the flag words.  An observation beyond the table (mu y above roughly
         1500) or below 2^-900 is bad for that draw (``nbad``, total -inf).
         ``accumulate`` continues the same WAIC state as ``loglik_blocks``."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd = S_all.shape[0]
-        if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
-            raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
         tot = np.zeros(4 * nd, np.int64)
         flags = np.zeros(nd, np.int32)
         pw = np.full((nd, self.count), np.nan) if pointwise else None
         if self.L.pht_ctx_loglik_unif(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), int(batch), tot,
                                       pw.ctypes.data if pointwise else None, int(bool(accumulate)), flags) != 0:
             raise _err(self.L)
-        tot = tot.reshape(nd, 4)
-        bad_draw = flags != 0
-        out = dict(H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(),
-                   bad_draw=bad_draw, flags=flags)
-        out["total"] = loglik_total(out["H"], out["F"], out["nbad"], bad_draw)
+        out = _totals_dict(tot, flags != 0, flags=flags)
         if pointwise:
             out["pointwise"] = pw
         return out
@@ -526,11 +540,8 @@ class Sweeper:
         whole.  ``grid_cap``: most blocks of the histogram kernel (0: the
         default); the result does not depend on it.  ``last_estep_ms`` then
         holds the device time of the histograms and of the contraction."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd, n = S_all.shape[0], self.n
-        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
-            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        n = self.n
+        S_all, s_all, nd = _pack_draws(S_list, s_list, n)
         ys = float(self.L.pht_estep_yscale(self.ymax)) if yscale is None else float(yscale)
         nw = self.L.pht_estep_words()
         tot = np.zeros(4 * nd, np.int64)
@@ -544,9 +555,7 @@ class Sweeper:
         if self.L.pht_ctx_estep(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), int(batch), ys, tot,
                                 words.ctypes.data, ptr(Z), ptr(N), ptr(E), ptr(A), flags) != 0:
             raise _err(self.L)
-        hm, cm = C.c_float(0), C.c_float(0)
-        self.L.pht_ctx_estep_ms(self.ctx, C.byref(hm), C.byref(cm))
-        self.last_estep_ms = (hm.value, cm.value)
+        self.last_estep_ms = _ms_pair(self.L.pht_ctx_estep_ms, self.ctx)
         tot = tot.reshape(nd, 4)
         out = dict(Z=Z, N=None if N is None else N.reshape(nd, n, n).transpose(0, 2, 1).copy(), E=E, A=A,
                    H=tot[:, 0].copy(), F=tot[:, 1].copy(), nbad=tot[:, 2].copy(), nobs=tot[:, 3].copy(), flags=flags,
@@ -569,12 +578,8 @@ class Sweeper:
         default and at most 1400 / the largest rate) is inf with Q_F_BEYOND;
         any other flag is NaN.  ``last_quantile_ms`` then holds the device
         time of the table kernel and of the searches."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd, n = S_all.shape[0], self.n
-        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
-            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
-        probs = np.ascontiguousarray(np.atleast_1d(probs), np.float64).reshape(-1)
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
+        probs =np.ascontiguousarray(np.atleast_1d(probs), np.float64).reshape(-1)
         P_ = len(probs)
         if P_ < 1:
             raise ValueError("need at least one probability")
@@ -585,9 +590,7 @@ class Sweeper:
                                    np.inf if tmax is None else float(tmax), int(batch), t.reshape(-1), lo.reshape(-1),
                                    hi.reshape(-1), nev.reshape(-1), flags.reshape(-1), dflags) != 0:
             raise _err(self.L)
-        tm, sm = C.c_float(0), C.c_float(0)
-        self.L.pht_ctx_quantile_ms(self.ctx, C.byref(tm), C.byref(sm))
-        self.last_quantile_ms = (tm.value, sm.value)
+        self.last_quantile_ms = _ms_pair(self.L.pht_ctx_quantile_ms, self.ctx)
         return dict(t=t, lo=lo, hi=hi, nev=nev, flags=flags, bad_draw=dflags != 0, draw_flags=dflags)
 
     def forecast_units(self) -> np.ndarray:
@@ -627,11 +630,7 @@ class Sweeper:
         most blocks of the kernel (0: the default); the result does not depend
         on it.  ``last_forecast_ms`` then holds the device time of the table
         kernel and of the evaluations."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd, n = S_all.shape[0], self.n
-        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
-            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
         h = np.ascontiguousarray(np.atleast_1d(horizons), np.float64).reshape(-1)
         H = len(h)
         idx = self.forecast_units()
@@ -646,9 +645,7 @@ class Sweeper:
                                    int(batch), words.reshape(-1), qsum.ctypes.data, cnt.ctypes.data,
                                    q.ctypes.data if pointwise else None, flags) != 0:
             raise _err(self.L)
-        tm, em = C.c_float(0), C.c_float(0)
-        self.L.pht_ctx_forecast_ms(self.ctx, C.byref(tm), C.byref(em))
-        self.last_forecast_ms = (tm.value, em.value)
+        self.last_forecast_ms = _ms_pair(self.L.pht_ctx_forecast_ms, self.ctx)
         return forecast_finalise(words, qsum, cnt, idx, flags, q)
 
     def condition(self, S_list, s_list, horizons=None, batch: int = 64, pointwise: bool = False, grid_cap: int = 0):
@@ -680,11 +677,8 @@ class Sweeper:
         small fleets).  D is a mean: the variance of the replacement count
         within a draw is not computed.  ``last_condition_ms`` then holds the
         device time of the table kernels and of the unit kernel."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd, n = S_all.shape[0], self.n
-        if nd < 1 or S_all.shape != (nd, n * n) or s_all.shape != (nd, n):
-            raise ValueError(f"need at least one draw, each S [{n}, {n}] and s [{n}]")
+        n = self.n
+        S_all, s_all, nd = _pack_draws(S_list, s_list, n)
         h = np.ascontiguousarray(np.atleast_1d([] if horizons is None else horizons), np.float64).reshape(-1)
         H = len(h)
         idx = self.forecast_units()
@@ -704,9 +698,7 @@ class Sweeper:
                                     phi.ctypes.data if pointwise else None, mrl.ctypes.data if pointwise else None,
                                     d.ctypes.data if pointwise and H else None, flags) != 0:
             raise _err(self.L)
-        tm, um = C.c_float(0), C.c_float(0)
-        self.L.pht_ctx_condition_ms(self.ctx, C.byref(tm), C.byref(um))
-        self.last_condition_ms = (tm.value, um.value)
+        self.last_condition_ms = _ms_pair(self.L.pht_ctx_condition_ms, self.ctx)
         return condition_finalise(words, scales, phisum, mrlsum, dsum, cnt, idx, flags, phi, mrl, d)
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
@@ -733,12 +725,8 @@ class Sweeper:
         and ranks add (``predict_combine``, or the int64 reduce ``gibbs`` is
         given, then ``predict_finalise``), ymin / ymax combine by min / max.
         At most 2^22 replicates per call: split longer runs by ``rep0``."""
-        S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-        s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-        nd = S_all.shape[0]
-        if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
-            raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
-        edges = np.zeros(0) if edges is None else np.ascontiguousarray(edges, np.float64).reshape(-1)
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
+        edges =np.zeros(0) if edges is None else np.ascontiguousarray(edges, np.float64).reshape(-1)
         ne, nrep = len(edges), int(nrep)
         if not 1 <= nrep <= PRED_MAX_REP:
             raise ValueError(f"nrep = {nrep} outside 1..2^22 (split a longer run by rep0)")
@@ -773,11 +761,7 @@ class Sweeper:
         (pht_ctx_loo_fill_unif / pht_ctx_loo_fill).  Returns int64
         [draws, 4] totals ``[H, F, nbad, nobs]`` and the bool ``bad_draw``."""
         if unif:
-            S_all = np.ascontiguousarray([np.asarray(S, np.float64).reshape(-1, order="F") for S in S_list])
-            s_all = np.ascontiguousarray([np.asarray(s, np.float64).reshape(-1) for s in s_list])
-            nd = S_all.shape[0]
-            if nd < 1 or S_all.shape != (nd, self.n * self.n) or s_all.shape != (nd, self.n):
-                raise ValueError(f"need at least one draw, each S [{self.n}, {self.n}] and s [{self.n}]")
+            S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
             tot, flags = np.zeros(4 * nd, np.int64), np.zeros(nd, np.int32)
             if self.L.pht_ctx_loo_fill_unif(self.ctx, int(row0), nd, S_all.reshape(-1), s_all.reshape(-1), int(batch),
                                             tot, flags) != 0:

@@ -42,7 +42,7 @@ UNIT_DEFINES = {5: ("PHT_PHILOX_UNROLL",), 20: ("PHT_PHILOX_UNROLL",),
                 10: ("PHT_ECS_PHILOX_UNROLL",), 15: ("PHT_MHRS_PHILOX_UNROLL", "PHT_ECS_PHILOX_UNROLL")}
 # the host runtime, one job per unit (csrc/host_internal.h lists them)
 HOST_UNITS = ("host_r.cpp", "host_params.cpp", "host_ctx.cpp", "host_chains.cpp", "host_rccl.cpp", "host_gibbs.cpp",
-              "host_resident.cpp", "host_loglik.cpp", "host_predict.cpp", "host_psis.cpp", "host_estep.cpp", "host_quantile.cpp",
+              "host_resident.cpp", "host_unif.cpp", "host_loglik.cpp", "host_predict.cpp", "host_psis.cpp", "host_estep.cpp", "host_quantile.cpp",
               "host_forecast.cpp", "host_condition.cpp")
 # (source, extra defines, extra device-compile flags) per object; the kernel
 # units first: the long compiles start first
@@ -73,7 +73,7 @@ HEADERS = ["pht_claim.h", "pht_device.h", "pht_env.h", "pht_kernels.h", "pht_ker
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
            "pht_loglik_args.h", "pht_loglik_unif_args.h", "pht_predict_args.h", "pht_psis_args.h", "pht_estep_args.h",
            "pht_quantile_args.h", "pht_forecast_args.h", "pht_condition_args.h",
-           "host_internal.h", "host_hip.h", "host_lists.h"]
+           "host_internal.h", "host_hip.h", "host_lists.h", "host_unif_plan.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
 

@@ -237,7 +237,7 @@ int pht::host::unif_table(pht_ctx *c, SweepArgs &a, double lmax, bool headroom) 
   a.uK = unif_rows(lmax);
   a.uymax = c->ymax;
   const long more = headroom ? unif_tab_doubles(c->n, std::min(kUnifMaxK, a.uK * 3 / 2)) : 0;
-  HIPCHK(ensure(c->obs.d_utab, c->obs.utab_cap, unif_tab_doubles(c->n, a.uK), more));
+  HIPCHK(ensure(c->obs.d_utab, unif_tab_doubles(c->n, a.uK), more));
   a.utab = c->obs.d_utab.get();
   return 0;
 }
@@ -370,16 +370,12 @@ int pht::host::ctx_enqueue(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep,
   if (debug) {
     pht_ctx::Dbg &g = c->dbg;
     const size_t cnt = c->count, n = c->n;
-    if (g.cap < c->count) {
-      g = pht_ctx::Dbg{};
-      HIPCHK(g.d_zq.alloc(cnt * n));
-      HIPCHK(g.d_N.alloc(cnt * n * n));
-      HIPCHK(g.d_B.alloc(cnt));
-      HIPCHK(g.d_pre.alloc(cnt));
-      HIPCHK(g.d_flags.alloc(cnt));
-      HIPCHK(g.d_ndraw.alloc(cnt));
-      g.cap = c->count;
-    }
+    HIPCHK(ensure(g.d_zq, cnt * n));
+    HIPCHK(ensure(g.d_N, cnt * n * n));
+    HIPCHK(ensure(g.d_B, cnt));
+    HIPCHK(ensure(g.d_pre, cnt));
+    HIPCHK(ensure(g.d_flags, cnt));
+    HIPCHK(ensure(g.d_ndraw, cnt));
     HIPCHK(hipMemsetAsync(g.d_zq.get(), 0, sizeof(long long) * cnt * n, st));
     HIPCHK(hipMemsetAsync(g.d_N.get(), 0, sizeof(int) * cnt * n * n, st));
     HIPCHK(hipMemsetAsync(g.d_B.get(), 0, sizeof(int) * cnt, st));

@@ -38,22 +38,11 @@ extern "C" int pht_estep_contract(int n, const double *S, const double *s, const
 }
 
 extern "C" int pht_ctx_estep_grid_cap(pht_ctx *c, int cap) {
-  if (!c || cap < 0) {
-    set_err("pht_ctx_estep_grid_cap: null context or negative cap");
-    return -1;
-  }
-  c->es_grid_cap = cap;
-  return 0;
+  return grid_cap_set("pht_ctx_estep_grid_cap", "null context or negative cap", c, &pht_ctx::es_grid_cap, cap);
 }
 
 extern "C" int pht_ctx_estep_ms(pht_ctx *c, float *hist_ms, float *contract_ms) {
-  if (!c) {
-    set_err("pht_ctx_estep_ms: null context");
-    return -1;
-  }
-  if (hist_ms) *hist_ms = c->es_ms[0];
-  if (contract_ms) *contract_ms = c->es_ms[1];
-  return 0;
+  return clock_read("pht_ctx_estep_ms", c, &pht_ctx::es_clk, hist_ms, contract_ms);
 }
 
 extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const double *s, int batch, double yscale,
@@ -91,57 +80,31 @@ extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const doub
   hipStream_t st = c->stream.get();
   ctx_drain(c);
   const int n = c->n, no = n * n + 3 * n;
-  if (!c->ll_grid_cap) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    c->ll_grid_cap = std::max(1, cus) * 4;
-  }
   /* one block a CU (its LDS), unless the caller caps the grid */
-  const int grid_cap = c->es_grid_cap > 0 ? c->es_grid_cap : std::max(1, c->ll_grid_cap / 4);
-  for (auto &e : c->es_ev)
-    if (!e) HIPCHK(e.create());
+  const int grid_cap = c->es_grid_cap > 0 ? c->es_grid_cap : cu_count(c);
+  if (grid_cap < 0) return -1;
 
-  std::vector<double> meta((size_t)ndraws * PHT_LLU_META);
-  int Kcall = 0;
-  for (int d = 0; d < ndraws; d++) {
-    double *m = meta.data() + (size_t)d * PHT_LLU_META;
-    const unsigned flag = pht_llu_meta(n, S + (size_t)d * n * n, s + (size_t)d * n, c->ymax, m);
-    if (flags_out) flags_out[d] = (int)flag;
-    Kcall = std::max(Kcall, (int)m[PHT_LLU_M_K]);
-  }
-  const int stride = 2 * (Kcall + 1);
-  const int bmax = std::min(batch, ndraws);
-  const size_t nS = (size_t)ndraws * n * n, ns = (size_t)ndraws * n;
-  HIPCHK(ensure(c->d_lluin, c->lluin_cap, nS + ns + meta.size()));
-  HIPCHK(ensure(c->d_llutab, c->llutab_cap, (size_t)bmax * stride));
-  HIPCHK(ensure(c->d_lltot, c->lltot_cap, (size_t)ndraws * PHT_LL_TOT));
-  HIPCHK(ensure(c->d_eswords, c->eswords_cap, (size_t)bmax * PHT_ES_WORDS));
-  if (contract) HIPCHK(ensure(c->d_esout, c->esout_cap, (size_t)bmax * no));
-  double *dS = c->d_lluin.get(), *ds = dS + nS, *dmeta = ds + ns;
-  HIPCHK(hipMemcpyAsync(dS, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ds, s, sizeof(double) * ns, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dmeta, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice, st));
+  const UnifPlan plan(n, ndraws, S, s, batch, flags_out, [&](int, const double *Sd, const double *sd, double *m) {
+    return pht_llu_meta(n, Sd, sd, c->ymax, m);
+  });
+  const int bmax = plan.bmax, stride = plan.stride;
+  if (unif_stage(c, plan, S, s)) return -1;
+  HIPCHK(ensure(c->d_lltot, (size_t)ndraws * PHT_LL_TOT));
+  HIPCHK(ensure(c->d_eswords, (size_t)bmax * PHT_ES_WORDS));
+  if (contract) HIPCHK(ensure(c->d_esout, (size_t)bmax * no));
   HIPCHK(hipMemsetAsync(c->d_lltot.get(), 0, sizeof(unsigned long long) * (size_t)ndraws * PHT_LL_TOT, st));
   std::vector<double> hout(contract ? (size_t)bmax * no : 0);
-  c->es_ms[0] = c->es_ms[1] = 0.f;
+  PhaseClock &clk = c->es_clk;
+  if (clk.begin()) return -1;
   for (int d0 = 0; d0 < ndraws; d0 += batch) {
     const int nb = std::min(batch, ndraws - d0);
-    int Kmax = 0;
-    for (int d = d0; d < d0 + nb; d++) Kmax = std::max(Kmax, (int)meta[(size_t)d * PHT_LLU_META + PHT_LLU_M_K]);
     HIPCHK(hipMemsetAsync(c->d_eswords.get(), 0, sizeof(long long) * (size_t)nb * PHT_ES_WORDS, st));
-    HIPCHK(hipEventRecord(c->es_ev[0].get(), st));
-    LlunifTableArgs t{};
-    t.n = n;
-    t.nd = nb;
-    t.S = dS + (size_t)d0 * n * n;
-    t.s = ds + (size_t)d0 * n;
-    t.meta = dmeta + (size_t)d0 * PHT_LLU_META;
-    t.tab = c->d_llutab.get();
-    t.stride = stride;
-    HIPCHK(pht_launch_llunif_table(&t, st));
+    if (clk.mark(0, st)) return -1;
+    LlunifTableArgs t;
+    if (unif_tables(c, plan, d0, nb, t)) return -1;
     EstepHistArgs a{};
     a.nd = nb;
-    a.Kmax = Kmax;
+    a.Kmax = plan.Kmax(d0, nb);
     a.count = c->count;
     a.y = c->obs.d_y.get();
     a.cens = c->obs.d_cens.get();
@@ -152,7 +115,7 @@ extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const doub
     a.totals = c->d_lltot.get() + (size_t)d0 * PHT_LL_TOT;
     a.words = reinterpret_cast<unsigned long long *>(c->d_eswords.get());
     HIPCHK(pht_launch_estep_hist(&a, grid_cap, st));
-    HIPCHK(hipEventRecord(c->es_ev[1].get(), st));
+    if (clk.mark(1, st)) return -1;
     if (contract) {
       EstepContractArgs k{};
       k.n = n;
@@ -167,7 +130,7 @@ extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const doub
       k.out = c->d_esout.get();
       HIPCHK(pht_launch_estep_contract(&k, st));
     }
-    HIPCHK(hipEventRecord(c->es_ev[2].get(), st));
+    if (clk.mark(2, st)) return -1;
     if (contract)
       HIPCHK(hipMemcpyAsync(hout.data(), c->d_esout.get(), sizeof(double) * (size_t)nb * no, hipMemcpyDeviceToHost,
                             st));
@@ -175,11 +138,7 @@ extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const doub
       HIPCHK(hipMemcpyAsync(words + (size_t)d0 * PHT_ES_WORDS, c->d_eswords.get(),
                             sizeof(long long) * (size_t)nb * PHT_ES_WORDS, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    float ms0 = 0.f, ms1 = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms0, c->es_ev[0].get(), c->es_ev[1].get()));
-    HIPCHK(hipEventElapsedTime(&ms1, c->es_ev[1].get(), c->es_ev[2].get()));
-    c->es_ms[0] += ms0;
-    c->es_ms[1] += ms1;
+    if (clk.add_after_sync()) return -1;
     for (int d = 0; contract && d < nb; d++) {
       const double *o = hout.data() + (size_t)d * no;
       memcpy(Z + (size_t)(d0 + d) * n, o, sizeof(double) * n);
@@ -188,7 +147,7 @@ extern "C" int pht_ctx_estep(pht_ctx *c, int ndraws, const double *S, const doub
       memcpy(A + (size_t)(d0 + d) * n, o + 2 * n + n * n, sizeof(double) * n);
     }
   }
-  c->last_ms = c->es_ms[0] + c->es_ms[1];
+  c->last_ms = clk.total();
   HIPCHK(hipMemcpyAsync(totals, c->d_lltot.get(), sizeof(long long) * (size_t)ndraws * PHT_LL_TOT,
                         hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

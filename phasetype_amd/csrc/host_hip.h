@@ -68,16 +68,21 @@ struct Event : Owned<hipEvent_t, hipEventDestroy> {
   hipError_t create_untimed() { return hipEventCreateWithFlags(&h_, hipEventDisableTiming); }
 };
 
-/* device memory: count elements of T, uninitialised */
+/* device memory: count elements of T, uninitialised; cap(): that count (0 when empty) */
 template <class T>
-struct DevBuf : Owned<void *, hipFree> {
+class DevBuf : public Owned<void *, hipFree> {
+  size_t cap_ = 0;
+
+ public:
   hipError_t alloc(size_t count) {
     reset();
     const hipError_t e = hipMalloc(&h_, sizeof(T) * count);
     if (e != hipSuccess) h_ = nullptr;
+    cap_ = count;
     return e;
   }
   T *get() const { return static_cast<T *>(h_); }
+  size_t cap() const { return h_ ? cap_ : 0; }
 };
 
 /* pinned host memory (hipHostMalloc flags); mapped: with its device alias */
@@ -98,17 +103,12 @@ class PinnedBuf : public Owned<void *, hipHostFree> {
   T *dev() const { return h_ ? static_cast<T *>(dev_) : nullptr; } /* the mapped alias, if mapped */
 };
 
-/* the grow pattern: buf holds cap elements; when need exceeds that, free it
- * and allocate max(need, headroom) (contents are not kept).  On failure the
- * buffer is empty and cap is 0. */
-template <class T, class Cap>
-hipError_t ensure(DevBuf<T> &buf, Cap &cap, size_t need, size_t headroom = 0) {
-  if (need <= (size_t)cap) return hipSuccess;
-  cap = 0;
-  const size_t count = std::max(need, headroom);
-  const hipError_t e = buf.alloc(count);
-  if (e == hipSuccess) cap = (Cap)count;
-  return e;
+/* the grow pattern: when need exceeds buf.cap(), free it and allocate
+ * max(need, headroom) (contents are not kept).  On failure the buffer is
+ * empty and its cap() is 0. */
+template <class T>
+hipError_t ensure(DevBuf<T> &buf, size_t need, size_t headroom = 0) {
+  return need <= buf.cap() ? hipSuccess : buf.alloc(std::max(need, headroom));
 }
 
 }  // namespace host

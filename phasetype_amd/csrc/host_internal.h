@@ -11,6 +11,7 @@
  *   host_rccl.cpp      RCCL binding and its entry points
  *   host_gibbs.cpp     Gibbs bookkeeping and loop, pht_gibbs_run, pht_theta_to_S
  *   host_resident.cpp  pht_gibbs_run_resident
+ *   host_unif.cpp      what the uniformisation analyses share: staging (host_unif_plan.h), PhaseClock, grids
  *   host_loglik.cpp    log-likelihood blocks, pht_ctx_loglik* and pht_ctx_loglik_unif*
  *   host_predict.cpp   posterior-predictive replicates, pht_pred_* and pht_ctx_predict
  *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
@@ -34,8 +35,10 @@
 #include "../../include/phasetype_amd.h"
 #include "host_hip.h"
 #include "host_lists.h"
+#include "host_unif_plan.h"
 #include "pht_kernels.h"
 #include "pht_layout.h"
+#include "pht_loglik_unif_args.h"
 #include "rstream.h"
 
 #pragma GCC visibility push(hidden)
@@ -120,6 +123,17 @@ inline int dispatch_method(int method) {
 
 struct ChainGroup;
 
+/* the device time of a call in two phases, summed over its batches: three
+ * events (created on first use) and the two sums */
+struct PhaseClock {
+  Event ev[3];
+  float ms[2] = {0.f, 0.f};
+  int begin();                            /* a call starts: the events exist, the sums are zero */
+  int mark(int i, hipStream_t st);        /* record event i */
+  int add_after_sync();                   /* the batch is through: ms[0] += ev0..ev1, ms[1] += ev1..ev2 */
+  float total() const { return ms[0] + ms[1]; }
+};
+
 }  // namespace host
 }  // namespace pht
 
@@ -154,13 +168,11 @@ struct pht_ctx {
     DevBuf<uint32_t> d_mbest, d_mq0, d_mq1;
     DevBuf<unsigned> d_mcnt;
     DevBuf<double> d_utab;               /* UNIF per-sweep table (pht_unif.h) */
-    long utab_cap = 0;                   /* its capacity in doubles */
     DevBuf<int> d_dcsb;                  /* DCS: per-position end states (dcs_end_kernel) */
     /* pht_ctx_loglik: the pointwise staging buffer, and the WAIC state per
      * observation in the device (sorted) order: 5 double arrays
      * [ref S1 S2 m r] and the counts */
     DevBuf<double> d_llpw;
-    size_t llpw_cap = 0;
     DevBuf<double> d_waic;
     DevBuf<long long> d_wcnt;
     /* pht_ctx_loo_*: the pointwise matrix [ndraws][count] in the device
@@ -185,7 +197,6 @@ struct pht_ctx {
       std::vector<long> idx, rank;
       DevBuf<double> d_age, d_qsum, d_q;
       DevBuf<int> d_cnt;
-      size_t qsum_cap = 0, cnt_cap = 0, q_cap = 0;
     } fc;
   } obs;
   DevBuf<unsigned char> d_params;
@@ -202,7 +213,6 @@ struct pht_ctx {
     DevBuf<long long> d_zq;
     DevBuf<int> d_N, d_B, d_pre, d_flags;
     DevBuf<uint32_t> d_ndraw;
-    long cap = 0;
   } dbg;
 #ifdef PHT_BLOCK_TIMES
   /* variant builds: the ECS exact kernel's per-block records of the last
@@ -243,15 +253,10 @@ struct pht_ctx {
   PinnedBuf<unsigned> h_gate;
   PinnedBuf<unsigned char> h_pg;
   unsigned gate_seq = 0;
+  int cus = 0; /* the device's CU count, read once (cu_count): the default grids derive from it */
   /* pht_ctx_loglik (allocated on first use): draw blocks and totals of a call */
   DevBuf<double> d_llblk;
   DevBuf<unsigned long long> d_lltot;
-  long llblk_cap = 0, lltot_cap = 0;
-  int ll_grid_cap = 0;
-  /* pht_ctx_loglik_unif: a call's (S, s, meta words) and one batch's tables
-   * [draw][k][2]; its own buffer, never the sampler's obs.d_utab */
-  DevBuf<double> d_lluin, d_llutab;
-  size_t lluin_cap = 0, llutab_cap = 0;
   /* pht_ctx_predict (allocated on first use; its own buffers, never the
    * sampler's): a call's tables + edges, flags, result words ([nd][8] sums,
    * [nd] ymin, [nd] ymax, [nd][ne + 1] counts) and one batch's pointwise
@@ -259,55 +264,44 @@ struct pht_ctx {
   DevBuf<double> d_predin, d_predy;
   DevBuf<int> d_predflag, d_prednj;
   DevBuf<unsigned long long> d_predout;
-  size_t predin_cap = 0, predy_cap = 0, predflag_cap = 0, prednj_cap = 0, predout_cap = 0;
-  /* pht_ctx_estep (allocated on first use; its own buffers and events, never
-   * the sampler's): one batch's int64 words [draw][class][k][G, T] and results
-   * [draw][Z n, N n n, E n]; the tables and totals are the log-likelihood's
-   * (d_lluin, d_llutab, d_lltot).  es_grid_cap: 0 = one block a CU
-   * (pht_ctx_estep_grid_cap); es_ms: the last call's device time, histograms
-   * (with the tables) and contraction */
+  /* pht_ctx_loglik_unif and the analyses below evaluate draws through the
+   * uniformisation table and share its staging (host_unif.cpp): a call's (S, s,
+   * meta words) in d_lluin and one batch's tables [draw][k][2] in d_llutab, the
+   * context's own, never the sampler's obs.d_utab.  What each adds is allocated
+   * on first use and its own too, never the sampler's or the WAIC state's;
+   * X_grid_cap: 0 = the default grid (pht_ctx_X_grid_cap), X_clk: the last
+   * call's device time. */
+  DevBuf<double> d_lluin, d_llutab;
+  /* pht_ctx_estep: one batch's int64 words [draw][class][k][G, T] and results
+   * [draw][Z n, N n n, E n]; the totals are the log-likelihood's (d_lltot).
+   * Default grid: one block a CU; clock: histograms (with the tables) and
+   * contraction */
   DevBuf<long long> d_eswords;
   DevBuf<double> d_esout;
-  size_t eswords_cap = 0, esout_cap = 0;
   int es_grid_cap = 0;
-  float es_ms[2] = {0.f, 0.f};
-  Event es_ev[3];
-  /* pht_ctx_quantile (allocated on first use; its own buffers and events,
-   * never the sampler's or the WAIC state's): a call's sorted probabilities
-   * and horizons, one batch's results [t, lo, hi][draw][p] and [nev,
-   * flags][draw][p]; the draws and tables go through d_lluin and d_llutab as
-   * the E-step's do.  q_ms: the last call's device time, tables and searches */
+  pht::host::PhaseClock es_clk;
+  /* pht_ctx_quantile: a call's sorted probabilities and horizons, one batch's
+   * results [t, lo, hi][draw][p] and [nev, flags][draw][p].  Clock: tables
+   * and searches */
   DevBuf<double> d_qin, d_qout;
   DevBuf<int> d_qouti;
-  size_t qin_cap = 0, qout_cap = 0, qouti_cap = 0;
-  float q_ms[2] = {0.f, 0.f};
-  Event q_ev[3];
-  /* pht_ctx_forecast (allocated on first use; its own buffers and events,
-   * never the sampler's or the WAIC state's): a call's horizons and words
-   * [draw][horizon][4]; the units and their state are obs.fc's, the draws and
-   * tables go through d_lluin and d_llutab.  fc_grid_cap: 0 = two blocks a CU
-   * (pht_ctx_forecast_grid_cap); fc_ms: the last call's device time, tables
-   * and evaluations */
+  pht::host::PhaseClock q_clk;
+  /* pht_ctx_forecast: a call's horizons and words [draw][horizon][4]; the
+   * units and their state are obs.fc's.  Default grid: two blocks a CU; clock:
+   * tables and evaluations */
   DevBuf<double> d_fch;
   DevBuf<unsigned long long> d_fcwords;
-  size_t fch_cap = 0, fcwords_cap = 0;
   int fc_grid_cap = 0;
-  float fc_ms[2] = {0.f, 0.f};
-  Event fc_ev[3];
-  /* pht_ctx_condition (allocated on first use; its own buffers and events,
-   * never the sampler's, the WAIC state's or the forecast's): one batch's
+  pht::host::PhaseClock fc_clk;
+  /* pht_ctx_condition (never the forecast's buffers either): one batch's
    * forward tables [draw][k][n], a call's vectors [draw][m, r, scales] and
    * words [draw][n + nh + 3], the units' sums [unit][n + 2 + nh] and one
    * batch's pointwise values [unit][draw][n + 1 + nh]; the units are obs.fc's
-   * (read only), the draws and (ax, ac) tables go through d_lluin and
-   * d_llutab.  cd_grid_cap: 0 = two blocks a CU (pht_ctx_condition_grid_cap);
-   * cd_ms: the last call's device time, tables and units */
+   * (read only).  Default grid: two blocks a CU; clock: tables and units */
   DevBuf<double> d_cdF, d_cdvec, d_cdstate, d_cdpw;
   DevBuf<unsigned long long> d_cdwords;
-  size_t cdF_cap = 0, cdvec_cap = 0, cdstate_cap = 0, cdpw_cap = 0, cdwords_cap = 0;
   int cd_grid_cap = 0;
-  float cd_ms[2] = {0.f, 0.f};
-  Event cd_ev[3];
+  pht::host::PhaseClock cd_clk;
 };
 
 namespace pht {
@@ -332,6 +326,30 @@ int ctx_enqueue(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep, int zexp, 
 int ctx_wait(pht_ctx *c);
 void ctx_drain(pht_ctx *c);
 void ctx_release(pht_ctx *c, unsigned gate, const unsigned char *pb, size_t bytes);
+
+/* ================================ uniformisation analyses (host_unif.cpp) */
+/* the context's CU count (at least 1), read from the device once; < 0: failed */
+int cu_count(pht_ctx *c);
+/* d_lluin and d_llutab hold plan p; S, s and its meta words go up on the
+ * context's stream */
+int unif_stage(pht_ctx *c, const UnifPlan &p, const double *S, const double *s);
+/* the table kernel over the batch [d0, d0 + nb) of the staged plan; t: its
+ * arguments (t.S, t.s, t.meta, t.tab are what the analysis' own kernels read) */
+int unif_tables(pht_ctx *c, const UnifPlan &p, int d0, int nb, LlunifTableArgs &t);
+/* the bodies of pht_ctx_X_ms and pht_ctx_X_grid_cap (bad: the refusal's text after "who: ") */
+int clock_read(const char *who, const pht_ctx *c, const PhaseClock pht_ctx::*clk, float *ms0, float *ms1);
+int grid_cap_set(const char *who, const char *bad, pht_ctx *c, int pht_ctx::*cap, int value);
+
+/* ======================= the censored units (host_forecast.cpp), as the
+ * forecast and the condition take them */
+/* the context's censored units listed (once per pht_ctx_set_obs), at least
+ * one and at most max_units */
+int censored_units(pht_ctx *c, const char *who, long max_units);
+bool horizons_ok(const char *who, int nh, const double *h, int min_nh, int max_nh, int (*spec_ok)(int, const double *));
+/* the _host twins' units: 1 <= ncens <= max_units; ymax_c 0 or finite and at
+ * least the largest age (*ymax: the age the tables are sized for) */
+bool units_ok(const char *who, long ncens, long max_units);
+bool ymax_c_ok(const char *who, long ncens, const double *ages, double ymax_c, double *ymax);
 
 /* =============================================== chains (host_chains.cpp) */
 int group_sweep(pht_ctx *c, uint32_t k0, uint32_t k1, uint32_t sweep, int zexp);

@@ -174,14 +174,10 @@ static int loglik_batches(pht_ctx *c, int ndraws, int batch, long long *totals, 
                           double *dev_rows, Launch launch) {
   hipStream_t st = c->stream.get();
   const long count = c->count;
-  if (!c->ll_grid_cap) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    c->ll_grid_cap = std::max(1, cus) * 4;
-  }
-  HIPCHK(ensure(c->d_lltot, c->lltot_cap, (size_t)ndraws * PHT_LL_TOT));
+  if (cu_count(c) < 0) return -1;
+  HIPCHK(ensure(c->d_lltot, (size_t)ndraws * PHT_LL_TOT));
   const int bmax = std::min(batch, ndraws);
-  if (pointwise) HIPCHK(ensure(c->obs.d_llpw, c->obs.llpw_cap, (size_t)bmax * (size_t)count));
+  if (pointwise) HIPCHK(ensure(c->obs.d_llpw, (size_t)bmax * (size_t)count));
   if (accumulate && loglik_waic(c, false)) return -1;
   HIPCHK(hipMemsetAsync(c->d_lltot.get(), 0, sizeof(unsigned long long) * (size_t)ndraws * PHT_LL_TOT, st));
   std::vector<double> hpw;
@@ -234,7 +230,7 @@ static int loglik_spectral(pht_ctx *c, const char *who, int ndraws, const unsign
   hipStream_t st = c->stream.get();
   ctx_drain(c);
   const int n = c->n, words = pht_ll_words(n);
-  HIPCHK(ensure(c->d_llblk, c->llblk_cap, (size_t)ndraws * words));
+  HIPCHK(ensure(c->d_llblk, (size_t)ndraws * words));
   HIPCHK(hipMemcpyAsync(c->d_llblk.get(), blocks, 8 * (size_t)ndraws * words, hipMemcpyHostToDevice, st));
   return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, dev_rows,
                         [&](int d0, int nb, const LoglikOut &o) {
@@ -254,7 +250,7 @@ static int loglik_spectral(pht_ctx *c, const char *who, int ndraws, const unsign
     a.w_m = o.w_m;
     a.w_r = o.w_r;
     a.w_cnt = o.w_cnt;
-    HIPCHK(pht_launch_loglik(&a, c->ll_grid_cap, st));
+    HIPCHK(pht_launch_loglik(&a, 4 * c->cus, st));
     return 0;
   });
 }
@@ -284,48 +280,25 @@ static int loglik_unif(pht_ctx *c, const char *who, int ndraws, const double *S,
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream.get();
   ctx_drain(c);
-  const int n = c->n;
   /* the draws' meta words (flags, mu, K from the shard's largest y); the table
    * buffer holds one batch: every draw at the stride of the call's largest K */
-  std::vector<double> meta((size_t)ndraws * PHT_LLU_META);
-  int Kcall = 0;
-  for (int d = 0; d < ndraws; d++) {
-    double *m = meta.data() + (size_t)d * PHT_LLU_META;
-    const unsigned flag = pht_llu_meta(n, S + (size_t)d * n * n, s + (size_t)d * n, c->ymax, m);
-    if (flags_out) flags_out[d] = (int)flag;
-    Kcall = std::max(Kcall, (int)m[PHT_LLU_M_K]);
-  }
-  const int stride = 2 * (Kcall + 1);
-  const int bmax = std::min(batch, ndraws);
-  const size_t nS = (size_t)ndraws * n * n, ns = (size_t)ndraws * n;
-  HIPCHK(ensure(c->d_lluin, c->lluin_cap, nS + ns + meta.size()));
-  HIPCHK(ensure(c->d_llutab, c->llutab_cap, (size_t)bmax * stride));
-  double *dS = c->d_lluin.get(), *ds = dS + nS, *dmeta = ds + ns;
-  HIPCHK(hipMemcpyAsync(dS, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ds, s, sizeof(double) * ns, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dmeta, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice, st));
+  const UnifPlan plan(c->n, ndraws, S, s, batch, flags_out, [&](int, const double *Sd, const double *sd, double *m) {
+    return pht_llu_meta(c->n, Sd, sd, c->ymax, m);
+  });
+  if (unif_stage(c, plan, S, s)) return -1;
   return loglik_batches(c, ndraws, batch, totals, pointwise, accumulate, dev_rows,
                         [&](int d0, int nb, const LoglikOut &o) {
-    int Kmax = 0;
-    for (int d = d0; d < d0 + nb; d++) Kmax = std::max(Kmax, (int)meta[(size_t)d * PHT_LLU_META + PHT_LLU_M_K]);
-    LlunifTableArgs t{};
-    t.n = n;
-    t.nd = nb;
-    t.S = dS + (size_t)d0 * n * n;
-    t.s = ds + (size_t)d0 * n;
-    t.meta = dmeta + (size_t)d0 * PHT_LLU_META;
-    t.tab = c->d_llutab.get();
-    t.stride = stride;
-    HIPCHK(pht_launch_llunif_table(&t, st));
+    LlunifTableArgs t;
+    if (unif_tables(c, plan, d0, nb, t)) return -1;
     LlunifArgs a{};
     a.nd = nb;
-    a.Kmax = Kmax;
+    a.Kmax = plan.Kmax(d0, nb);
     a.count = c->count;
     a.y = c->obs.d_y.get();
     a.cens = c->obs.d_cens.get();
     a.meta = t.meta;
     a.tab = t.tab;
-    a.stride = stride;
+    a.stride = t.stride;
     a.totals = o.totals;
     a.pw = o.pw;
     a.acc = o.acc;
@@ -336,7 +309,7 @@ static int loglik_unif(pht_ctx *c, const char *who, int ndraws, const double *S,
     a.w_r = o.w_r;
     a.w_cnt = o.w_cnt;
     /* (under 64 KB of LDS a block: two blocks a CU, half the spectral kernel's cap) */
-    HIPCHK(pht_launch_llunif(&a, std::max(1, c->ll_grid_cap / 2), st));
+    HIPCHK(pht_launch_llunif(&a, 2 * c->cus, st));
     return 0;
   });
 }

@@ -113,12 +113,12 @@ extern "C" int pht_ctx_predict(pht_ctx *c, int nd, const double *S, const double
   for (int d = 0; d < nd; d++) hout[o_min + d] = 0x7ff0000000000000ull; /* +inf */
 
   const int bmax = std::min(batch, nd);
-  HIPCHK(ensure(c->d_predin, c->predin_cap, hin.size()));
-  HIPCHK(ensure(c->d_predflag, c->predflag_cap, (size_t)nd));
-  HIPCHK(ensure(c->d_predout, c->predout_cap, hout.size()));
+  HIPCHK(ensure(c->d_predin, hin.size()));
+  HIPCHK(ensure(c->d_predflag, (size_t)nd));
+  HIPCHK(ensure(c->d_predout, hout.size()));
   if (pw) {
-    HIPCHK(ensure(c->d_predy, c->predy_cap, (size_t)bmax * (size_t)nrep));
-    HIPCHK(ensure(c->d_prednj, c->prednj_cap, (size_t)bmax * (size_t)nrep));
+    HIPCHK(ensure(c->d_predy, (size_t)bmax * (size_t)nrep));
+    HIPCHK(ensure(c->d_prednj, (size_t)bmax * (size_t)nrep));
   }
   HIPCHK(hipMemcpyAsync(c->d_predin.get(), hin.data(), sizeof(double) * hin.size(), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(c->d_predflag.get(), hflag.data(), sizeof(int) * (size_t)nd, hipMemcpyHostToDevice, st));

@@ -44,13 +44,7 @@ extern "C" int pht_quantile_host(int n, const double *S, const double *s, int np
 }
 
 extern "C" int pht_ctx_quantile_ms(pht_ctx *c, float *table_ms, float *search_ms) {
-  if (!c) {
-    set_err("pht_ctx_quantile_ms: null context");
-    return -1;
-  }
-  if (table_ms) *table_ms = c->q_ms[0];
-  if (search_ms) *search_ms = c->q_ms[1];
-  return 0;
+  return clock_read("pht_ctx_quantile_ms", c, &pht_ctx::q_clk, table_ms, search_ms);
 }
 
 extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const double *s, int np, const double *probs,
@@ -73,8 +67,6 @@ extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const d
   hipStream_t st = c->stream.get();
   ctx_drain(c);
   const int n = c->n;
-  for (auto &e : c->q_ev)
-    if (!e) HIPCHK(e.create());
 
   /* the probabilities once in ascending order (NaN last; equal ones keep the
    * caller's order): neighbouring lanes then walk neighbouring windows */
@@ -88,48 +80,29 @@ extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const d
   std::vector<double> psort(np);
   for (int i = 0; i < np; i++) psort[i] = probs[perm[i]];
 
-  std::vector<double> meta((size_t)ndraws * PHT_LLU_META), thi(ndraws);
-  int Kcall = 0;
-  for (int d = 0; d < ndraws; d++) {
-    double *m = meta.data() + (size_t)d * PHT_LLU_META;
-    const unsigned flag = pht_q_meta(n, S + (size_t)d * n * n, s + (size_t)d * n, tmax, m, &thi[d]);
-    if (draw_flags_out) draw_flags_out[d] = (int)flag;
-    Kcall = std::max(Kcall, (int)m[PHT_LLU_M_K]);
-  }
-  const int stride = 2 * (Kcall + 1);
-  const int bmax = std::min(batch, ndraws);
-  const size_t nS = (size_t)ndraws * n * n, ns = (size_t)ndraws * n, cells = (size_t)bmax * np;
-  HIPCHK(ensure(c->d_lluin, c->lluin_cap, nS + ns + meta.size()));
-  HIPCHK(ensure(c->d_llutab, c->llutab_cap, (size_t)bmax * stride));
-  HIPCHK(ensure(c->d_qin, c->qin_cap, (size_t)np + ndraws));
-  HIPCHK(ensure(c->d_qout, c->qout_cap, 3 * cells));
-  HIPCHK(ensure(c->d_qouti, c->qouti_cap, 2 * cells));
-  double *dS = c->d_lluin.get(), *ds = dS + nS, *dmeta = ds + ns;
+  std::vector<double> thi(ndraws);
+  const UnifPlan plan(n, ndraws, S, s, batch, draw_flags_out, [&](int d, const double *Sd, const double *sd, double *m) {
+    return pht_q_meta(n, Sd, sd, tmax, m, &thi[d]);
+  });
+  const size_t cells = (size_t)plan.bmax * np;
+  if (unif_stage(c, plan, S, s)) return -1;
+  HIPCHK(ensure(c->d_qin, (size_t)np + ndraws));
+  HIPCHK(ensure(c->d_qout, 3 * cells));
+  HIPCHK(ensure(c->d_qouti, 2 * cells));
   double *dprobs = c->d_qin.get(), *dthi = dprobs + np;
-  HIPCHK(hipMemcpyAsync(dS, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ds, s, sizeof(double) * ns, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dmeta, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dprobs, psort.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dthi, thi.data(), sizeof(double) * ndraws, hipMemcpyHostToDevice, st));
   std::vector<double> hd(3 * cells);
   std::vector<int> hi(2 * cells);
-  c->q_ms[0] = c->q_ms[1] = 0.f;
+  PhaseClock &clk = c->q_clk;
+  if (clk.begin()) return -1;
   for (int d0 = 0; d0 < ndraws; d0 += batch) {
-    const int nb = std::min(batch, ndraws - d0);
-    int Kmax = 0;
-    for (int d = d0; d < d0 + nb; d++) Kmax = std::max(Kmax, (int)meta[(size_t)d * PHT_LLU_META + PHT_LLU_M_K]);
+    const int nb = std::min(batch, ndraws - d0), Kmax = plan.Kmax(d0, nb);
     const size_t nc = (size_t)nb * np;
-    HIPCHK(hipEventRecord(c->q_ev[0].get(), st));
-    LlunifTableArgs t{};
-    t.n = n;
-    t.nd = nb;
-    t.S = dS + (size_t)d0 * n * n;
-    t.s = ds + (size_t)d0 * n;
-    t.meta = dmeta + (size_t)d0 * PHT_LLU_META;
-    t.tab = c->d_llutab.get();
-    t.stride = stride;
-    HIPCHK(pht_launch_llunif_table(&t, st));
-    HIPCHK(hipEventRecord(c->q_ev[1].get(), st));
+    if (clk.mark(0, st)) return -1;
+    LlunifTableArgs t;
+    if (unif_tables(c, plan, d0, nb, t)) return -1;
+    if (clk.mark(1, st)) return -1;
     QuantileArgs a{};
     int pool = 1;
     a.nd = nb;
@@ -140,7 +113,7 @@ extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const d
     a.meta = t.meta;
     a.thi = dthi + d0;
     a.tab = t.tab;
-    a.stride = stride;
+    a.stride = t.stride;
     a.probs = dprobs;
     a.t0 = t0;
     a.t = c->d_qout.get();
@@ -149,15 +122,11 @@ extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const d
     a.nev = c->d_qouti.get();
     a.flags = reinterpret_cast<unsigned *>(a.nev + nc);
     HIPCHK(pht_launch_quantile(&a, st));
-    HIPCHK(hipEventRecord(c->q_ev[2].get(), st));
+    if (clk.mark(2, st)) return -1;
     HIPCHK(hipMemcpyAsync(hd.data(), c->d_qout.get(), sizeof(double) * 3 * nc, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hi.data(), c->d_qouti.get(), sizeof(int) * 2 * nc, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    float ms0 = 0.f, ms1 = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms0, c->q_ev[0].get(), c->q_ev[1].get()));
-    HIPCHK(hipEventElapsedTime(&ms1, c->q_ev[1].get(), c->q_ev[2].get()));
-    c->q_ms[0] += ms0;
-    c->q_ms[1] += ms1;
+    if (clk.add_after_sync()) return -1;
     /* back into the caller's order */
     for (int d = 0; d < nb; d++) {
       const size_t src = (size_t)d * np, dst = (size_t)(d0 + d) * np;
@@ -171,6 +140,6 @@ extern "C" int pht_ctx_quantile(pht_ctx *c, int ndraws, const double *S, const d
       }
     }
   }
-  c->last_ms = c->q_ms[0] + c->q_ms[1];
+  c->last_ms = clk.total();
   return 0;
 }
