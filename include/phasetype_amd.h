@@ -125,7 +125,9 @@ int pht_ctx_rccl_allreduce(pht_ctx *c, long long *buf, int len);
  * set.seed but not the host loop's chain.  Any method matching the context's
  * (for ECS/DCS the update also builds the eigensystem, include/pht_eigen.h,
  * instead of LAPACK: a complex spectrum stops the run with an error, where the
- * host path warns and uses the real parts as the reference does); an attached RCCL
+ * host path warns and uses the real parts as the reference does, and so does a
+ * defective or nearly defective S, whose eigenvectors do not reproduce it:
+ * PHT_EIG_RESID_TOL); an attached RCCL
  * communicator sums every sweep's statistics on the stream (every rank must
  * use the same R-stream seed).  Arguments and res layout as pht_gibbs_run;
  * kernel_ms_total = device time of all sweeps. */

@@ -24,6 +24,17 @@
  * the caller stops the chain (the uniformisation sampler is the path for
  * such generators).  Iteration caps keep every loop finite.
  *
+ * A defective S (tied total rates along a chain: Erlang, a Coxian with one
+ * rate) has no eigenvector basis, and a nearly defective one has a basis too
+ * ill-conditioned to carry the spectral products.  The method does not stop on
+ * either: the back-substitution divides by eps * norm where two eigenvalues
+ * coincide and the LU of the resulting Q almost never meets an exactly zero
+ * pivot.  So no eigensystem is handed out unverified: pht_eig and an accepted
+ * pht_eig_refine form R = max |Q diag(lambda) Q^-1 - S|, each element with
+ * the rounding bound of its own sum added (pht_eig_verify), and return
+ * PHT_EIG_SINGULAR unless R <= PHT_EIG_RESID_TOL max_j |S_jj|.  The
+ * outputs of an accepted eigensystem are those of the method alone.
+ *
  * Threads: every thread of the workgroup calls pht_eig with the same
  * arguments; scalars are computed redundantly from shared values, the loops
  * marked PHT_EIG_FOR are split over the threads, PHT_EIG_SYNC separates
@@ -52,7 +63,7 @@
 #define PHT_EIG_OK 0
 #define PHT_EIG_COMPLEX 1  /* a complex-conjugate pair */
 #define PHT_EIG_NOCONV 2   /* QR iteration cap (30 per eigenvalue, at least 300) */
-#define PHT_EIG_SINGULAR 3 /* eigenvector matrix singular (defective S) */
+#define PHT_EIG_SINGULAR 3 /* Q diag(lambda) Q^-1 does not reproduce S (defective or nearly defective S) */
 
 typedef struct {
   double *H, *V, *X; /* n*n each: Hessenberg/Schur form, transformations, triangular eigenvectors */
@@ -61,6 +72,11 @@ typedef struct {
 } pht_eig_ws;
 
 #define PHT_EIG_EPS 2.220446049250313080847e-16 /* 2^-52 */
+/* the largest accepted max |Q diag(lambda) Q^-1 - S| / max_j |S_jj|: the
+ * relative cancellation the spectral log-likelihood tolerates (PHT_LL_EMAX,
+ * include/pht_loglik.h; tests/test_eigen_structures.py holds the two equal).
+ * Measured margins: DESIGN.md, section 7d */
+#define PHT_EIG_RESID_TOL 0x1p-20
 
 /* Balancing by powers of 2 (EISPACK balanc without the permutations):
  * D^-1 S D with row and column 1-norms (off the diagonal) made comparable. */
@@ -353,9 +369,59 @@ PHT_HD int pht_eig_qr(int n, double *H, double *V, double *d) {
 }
 
 /*
+ * The acceptance check of an eigensystem: PHT_EIG_OK when
+ * R = max_ij (|sum_k t_ijk - S_ij| + eps sum_k |t_ijk|), t_ijk = Q_ik lambda_k Qinv_kj,
+ * is at most PHT_EIG_RESID_TOL max_j |S_jj|; PHT_EIG_SINGULAR otherwise (a NaN
+ * anywhere in the product included: the maxima below keep one).  The second
+ * term is the rounding error of the sum itself.  Where the terms are 1e18 and
+ * cancel, the computed sum is one of many values a different order would have
+ * given, and its distance to S_ij says nothing: the sum in this order is
+ * within 4e-8 of S for the Erlang-like chain with rates 1e-9 apart, 56 in
+ * another order, and the samplers' products Q exp(lambda y) Q^-1 cancel the
+ * same way.  The n^2 elements are split over the threads into
+ * R (n*n) and reduced per column into colv (n), both visible to the
+ * workgroup and distinct from the inputs; every thread then takes the same
+ * maximum of colv, so the verdict is uniform.
+ */
+PHT_HD int pht_eig_verify(int n, const double *S, const double *evals, const double *Q, const double *Qinv, double *R,
+                          double *colv) {
+  PHT_EIG_SYNC();
+  PHT_EIG_FOR(e, 0, n * n) {
+    const int i = e % n, j = e / n;
+    double acc = 0.0, ab = 0.0;
+    for (int k = 0; k < n; k++) {
+      const double t = (Q[i + k * n] * evals[k]) * Qinv[k + j * n];
+      acc = acc + t;
+      ab = ab + fabs(t);
+    }
+    R[e] = fabs(acc - S[e]) + PHT_EIG_EPS * ab;
+  }
+  PHT_EIG_SYNC();
+  PHT_EIG_FOR(j, 0, n) {
+    double m = 0.0;
+    for (int i = 0; i < n; i++) {
+      const double r = R[i + j * n];
+      if (r > m || r != r) m = r; /* (a NaN stays: no later r compares above it) */
+    }
+    colv[j] = m;
+  }
+  PHT_EIG_SYNC();
+  double res = 0.0, mu = 0.0;
+  for (int j = 0; j < n; j++) {
+    const double r = colv[j];
+    if (r > res || r != r) res = r;
+    mu = fmax(mu, fabs(S[j + j * n]));
+  }
+  PHT_EIG_SYNC(); /* every thread has read colv */
+  return (res <= PHT_EIG_RESID_TOL * mu) ? PHT_EIG_OK : PHT_EIG_SINGULAR;
+}
+
+/*
  * evals[n], Q (n x n, right eigenvectors as columns, unit 2-norm) and
  * Qinv = Q^-1 of S.  Returns PHT_EIG_OK or an error code (uniform over the
- * workgroup).  Q and Qinv may be any memory the workgroup can write.
+ * workgroup); PHT_EIG_OK only for an eigensystem that passed pht_eig_verify.
+ * Q and Qinv may be any memory the workgroup can write (not w's arrays, except
+ * that Qinv may be w->X).
  */
 PHT_HD int pht_eig(int n, const double *S, double *evals, double *Q, double *Qinv, pht_eig_ws *w) {
   double *H = w->H, *V = w->V, *X = w->X, *G = w->G, *d = w->d;
@@ -456,8 +522,8 @@ PHT_HD int pht_eig(int n, const double *S, double *evals, double *Q, double *Qin
       x[i] = acc / G[i + i * n];
     }
   }
-  PHT_EIG_SYNC();
-  return PHT_EIG_OK;
+  /* (H and ort are free since the back-transformation) */
+  return pht_eig_verify(n, S, evals, Q, Qinv, H, w->ort);
 }
 
 /* ------------------------------------------------------------------
@@ -477,6 +543,8 @@ PHT_HD int pht_eig(int n, const double *S, double *evals, double *Q, double *Qin
  * caller runs pht_eig) after PHT_EIG_REFINE_MAX rounds or when two diagonal
  * entries are closer than 2x the largest off-diagonal entry (the first-order
  * step needs |B_ki| well below |B_ii - B_kk|).
+ * An accepted refinement passes pht_eig_verify like the full QR's result
+ * (PHT_EIG_SINGULAR otherwise; the caller then runs pht_eig, which decides).
  * Outputs as pht_eig; Q is used as scratch until the end.
  */
 #define PHT_EIG_REFINE_MAX 12
@@ -584,8 +652,8 @@ PHT_HD int pht_eig_refine(int n, const double *S, const double *Q0, const double
     Q[e] = Z[e] / rowv[j];
     Qinv[e] = Zi[e] * rowv[i];
   }
-  PHT_EIG_SYNC();
-  return PHT_EIG_OK;
+  /* (T is free after the last round; rowv is read above: the check's first barrier comes before its writes) */
+  return pht_eig_verify(n, S, evals, Q, Qinv, T, rowv);
 }
 
 #endif /* PHT_EIGEN_H */

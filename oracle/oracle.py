@@ -149,6 +149,7 @@ class OracleLib:
         L.orc_eig.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
         L.orc_eig_refine.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
         L.orc_eig_fallback_count.restype = C.c_long
+        L.orc_dev_flagged_count.restype = C.c_long
         L.orc_set_dcs_brent.argtypes = [C.c_int]
         L.orc_set_bridge.argtypes = [C.c_int, C.c_int]
 

@@ -498,6 +498,12 @@ void orc_ref_sweep(const orc_sp *sp, int method, int mhit, const double *y, cons
   if (stats) { stats[0] += neval; stats[1] += nbrent; }
 }
 
+/* diagnostics: observations of the device-variant sweeps that hit a cap or a
+ * guard (flags != 0) since the last call (tests: a resident chain without
+ * flagged observations here must have none on the GPU) */
+static long orc_dev_flagged = 0;
+long orc_dev_flagged_count(void) { long v = orc_dev_flagged; orc_dev_flagged = 0; return v; }
+
 /*
  * Device-variant step 1 (the GPU specification): observation i draws from
  * its own Philox stream (key k0,k1; counter obs=obs0+i, tag 0, sweep).
@@ -535,6 +541,7 @@ void orc_dev_sweep(const orc_sp *sp, int method, int mhit, const double *y, cons
     else if (cens[i]) orcD_obs_censored(sp, y[i], cens[i], &r, &o, zscale, &neval);
     else orcD_obs_ecs_exact(sp, y[i], &r, &o, zscale, &neval);
     if (m != ORC_MHRS || ulaw) o.ndraw = pht_stream_pos(&r);
+    if (o.flags != 0) orc_dev_flagged++;
     B_tot[o.B]++;
     for (int k = 0; k < n; k++) zq_tot[k] += o.zq[k];
     for (int k = 0; k < n * n; k++) N_tot[k] += o.N[k];
@@ -653,8 +660,18 @@ void orc_gibbs_z(int dev, int it, int mhit, int method, int n, int m, const doub
   if (!dev && disp == ORC_UNIF) disp = 0;
   for (int iter = 1; iter < it; iter++) {
     if (!disp) continue; /* "CRITICAL ERROR: Unknown sampling method" */
-    orc_sp_build(sp, n, S, s,
-                 (disp == ORC_MHRS ? ORC_MHRS : method) | (dev == 2 ? ORC_DEVEIG | (iter > 1 ? ORC_DEVEIG_WARM : 0) : 0));
+    const int info = orc_sp_build(sp, n, S, s, (disp == ORC_MHRS ? ORC_MHRS : method) |
+                                                   (dev == 2 ? ORC_DEVEIG | (iter > 1 ? ORC_DEVEIG_WARM : 0) : 0));
+    if (dev == 2 && info != 0) {
+      /* the resident chain stops where its eigensystem (include/pht_eigen.h)
+       * refuses the S of row iter - 1 (the product reports an error and
+       * returns no chain): that row is the last one, NaN from here on.  The
+       * other variants follow the reference, which goes on whatever dgeevx
+       * reports */
+      for (int r = iter; r < it; r++)
+        for (int k = 0; k < m; k++) res[r + (size_t)k * it] = NAN;
+      break;
+    }
     if (!dev) {
       orc_ref_sweep(sp, method, mhit, y, censored, l, z, Bt, Nt, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
     } else {

@@ -210,7 +210,8 @@ extern "C" int pht_gibbs_run_resident(pht_ctx *c, int it, int method, int m, con
     set_err("resident chain: %s%s%s%s%s", (err & 1) ? "a sweep did not sample every observation; " : "",
             (err & 2) ? "the fixed-point z sums overflowed (pass a smaller zexp); " : "",
             (err & 4) ? "a Gamma draw failed (non-finite shape/scale or the rejection cap); " : "",
-            (err & 8) ? "the eigensystem failed (complex eigenvalues, no QR convergence or singular eigenvectors:"
+            (err & 8) ? "the eigensystem failed (complex eigenvalues, no QR convergence, or a defective or nearly "
+                        "defective S whose eigenvectors do not reproduce it:"
                         " the uniformisation sampler, method 8, needs none); " : "",
             (err & 16) ? "UNIF observations needed more uniformisation steps than the table sized from the start "
                          "(twice its largest exit rate) holds, or mu*y > 1300: the chain's rates drifted far above "

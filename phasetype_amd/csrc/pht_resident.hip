@@ -38,8 +38,9 @@ constexpr int kResMaxM = (kMaxN + 1) * (kMaxN + 1);
  * ECS/DCS: the spectral part of build_params (host_params.cpp; the
  * reference's src/PHT_MCMC_Aslett.c:320-332) from this sweep's S, s, P in
  * the parameter block: the eigensystem (include/pht_eigen.h: refined from
- * the previous sweep's, the full QR at init or when that fails) in place of
- * LAPACK, then Q^-1 s and Q^-1 1 in the reference BLAS dgemv order
+ * the previous sweep's, the full QR at init or when that fails; either is
+ * accepted only if Q diag(lambda) Q^-1 reproduces S, pht_eig_verify) in place
+ * of LAPACK, then Q^-1 s and Q^-1 1 in the reference BLAS dgemv order
  * and the products QQs, W, QQ1, V, piQ with build_params's fma order.  A
  * failed eigensystem sets err bit 3 and leaves the previous sweep's spectral
  * data in place (finite values; the host reports the error after the run);
