@@ -374,6 +374,53 @@ int pht_condition_host(int n, const double *S, const double *s, long ncens, cons
                        double *phisum, double *mrlsum, double *dsum, long long *cnt, double *phi_out, double *mrl_out,
                        double *d_out);
 
+/* Fleet spares (include/pht_spares.h is the whole definition): for every draw
+ * (S, s) with pi = e_1, every right-censored observation c_i of the context (a
+ * unit still in service at age c_i) and every horizon h_j, the mean D and the
+ * VARIANCE var of the number of failures within h_j when every failed unit is
+ * replaced by a new one (D is pht_ctx_condition's, bit for bit; var = Q + D -
+ * D^2 with Q = phi . q_h the second factorial moment).  The draws' moment
+ * vectors are built on the device.  No reference counterpart.  Limits: the
+ * condition's, and 1 to 16 horizons.
+ *
+ * pht_ctx_spares: ndraws draws as in pht_ctx_condition, `batch` (1..64) per
+ *   launch; nh (1..16) horizons.  words_out: int64 [ndraws][2 nh + 2] =
+ *   [Delta_0 .. Delta_{nh-1}, V_0 .. V_{nh-1}, nbad, nunits], the sums over the
+ *   units good for that draw of llrint((D_j / dscale_j) 2^40) and
+ *   llrint((var_j / vscale_j) 2^40) (exact integer sums: shards and ranks add
+ *   them; the units are independent given the draw, so V is the fleet's
+ *   variance within the draw); scales_out: [ndraws][2 nh] = [dscale_j,
+ *   vscale_j], powers of two that depend on the draw alone; both zero for a
+ *   flagged draw.  dsum_out, vsum_out, d2sum_out [ncens][nh] (double: the sums
+ *   of D, var and D D) and cnt_out [ncens] (int64), in the caller's order of
+ *   the censored observations and started from zero by every call: the sums
+ *   over the draws in which the unit was good, in draw order, and their
+ *   number.  d_out: NULL, or [ndraws][ncens][nh] with var_out of the same
+ *   shape, NaN where bad (tests and small fleets).  draw_flags_out (ndraws,
+ *   may be NULL): pht_ctx_condition's flag words for the same input; a flagged
+ *   draw is skipped.  Refused with a message: no censored observation on the
+ *   context, more than 2^22, nh or a horizon outside the above, batch outside
+ *   1..64.  The buffers are the context's own: its chain, its WAIC state, its
+ *   forecast state and its condition buffers are not affected.
+ * pht_ctx_spares_grid_cap: most blocks of the unit kernel (0: the default);
+ *   the result does not depend on it.
+ * pht_ctx_spares_ms: device time of the last call, the vectors kernel with
+ *   the table kernels, and the unit kernel.
+ * pht_spares_host: host only (no GPU), one draw over `ncens` ages; bit for
+ *   bit what the device computes.  ymax_c: the largest censored observation
+ *   the tables are sized for (0: the largest of ages).  words_out [2 nh + 2]
+ *   and scales_out [2 nh] are written; dsum, vsum, d2sum and cnt (may be NULL)
+ *   are UPDATED (one call per draw, in order); d_out, var_out (may be NULL)
+ *   are written.  Returns the draw's flag word, < 0 on error. */
+int pht_ctx_spares(pht_ctx *c, int ndraws, const double *S, const double *s, int nh, const double *horizons,
+                   int batch, long long *words_out, double *scales_out, double *dsum_out, double *vsum_out,
+                   double *d2sum_out, long long *cnt_out, double *d_out, double *var_out, int *draw_flags_out);
+int pht_ctx_spares_grid_cap(pht_ctx *c, int cap);
+int pht_ctx_spares_ms(pht_ctx *c, float *vector_ms, float *unit_ms);
+int pht_spares_host(int n, const double *S, const double *s, long ncens, const double *ages, int nh,
+                    const double *horizons, double ymax_c, long long *words_out, double *scales_out, double *dsum,
+                    double *vsum, double *d2sum, long long *cnt, double *d_out, double *var_out);
+
 /* PSIS-LOO cross-validation with Pareto-k diagnostics (include/pht_psis.h is
  * the whole definition): per observation, from l[d, i] of every usable draw
  * at once, elpd_loo_i, the Pareto shape khat_i of the importance ratios' tail

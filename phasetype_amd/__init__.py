@@ -34,7 +34,8 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "fleet_forecast", "forecast_combine", "forecast_finalise", "forecast_host", "forecast_moments",
            "forecast_count_quantiles", "FORECAST_MAX_H", "FORECAST_MAX_UNITS",
            "fleet_condition", "condition_combine", "condition_finalise", "condition_host", "ph_state", "ph_mrl",
-           "CONDITION_MAX_H", "CONDITION_MAX_UNITS", "CD_F_TRAP", "CD_F_HCAP"]
+           "CONDITION_MAX_H", "CONDITION_MAX_UNITS", "CD_F_TRAP", "CD_F_HCAP",
+           "fleet_spares", "spares_combine", "spares_finalise", "spares_host", "ph_renewal"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -71,6 +72,7 @@ EXPORTS = [
     "pht_ctx_forecast", "pht_ctx_forecast_units", "pht_ctx_forecast_grid_cap", "pht_ctx_forecast_ms",
     "pht_forecast_host",
     "pht_ctx_condition", "pht_ctx_condition_grid_cap", "pht_ctx_condition_ms", "pht_condition_host",
+    "pht_ctx_spares", "pht_ctx_spares_grid_cap", "pht_ctx_spares_ms", "pht_spares_host",
 ]
 
 
@@ -193,6 +195,12 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_condition_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pht_condition_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, _dp] + \
         [C.c_void_p] * 7
+    L.pht_ctx_spares.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _lp, _dp] + \
+        [C.c_void_p] * 6 + [_ip]
+    L.pht_ctx_spares_grid_cap.argtypes = [C.c_void_p, C.c_int]
+    L.pht_ctx_spares_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_spares_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, _dp] + \
+        [C.c_void_p] * 6
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -675,7 +683,7 @@ class Sweeper:
         skipped), and with ``pointwise`` ``phi`` [draws, units, n], ``mrl``
         [draws, units] and ``d`` [draws, units, H] (NaN where bad; for tests and
         small fleets).  D is a mean: the variance of the replacement count
-        within a draw is not computed.  ``last_condition_ms`` then holds the
+        within a draw is not computed here (``spares`` computes it).  ``last_condition_ms`` then holds the
         device time of the table kernels and of the unit kernel."""
         n = self.n
         S_all, s_all, nd = _pack_draws(S_list, s_list, n)
@@ -700,6 +708,51 @@ class Sweeper:
             raise _err(self.L)
         self.last_condition_ms = _ms_pair(self.L.pht_ctx_condition_ms, self.ctx)
         return condition_finalise(words, scales, phisum, mrlsum, dsum, cnt, idx, flags, phi, mrl, d)
+
+    def spares(self, S_list, s_list, horizons, batch: int = 64, pointwise: bool = False, grid_cap: int = 0):
+        """pht_ctx_spares: for each draw (S, s), each censored observation c_i of
+        this shard (a unit still in service at age c_i) and each of ``horizons``
+        (1 to 16 as in ``forecast``) the mean D and the variance of the number
+        of failures within h when every failed unit is replaced by a new one
+        (include/pht_spares.h; ``condition``'s limits apply, and D, ``dsum``,
+        ``Delta`` and ``flags`` are ``condition``'s bit for bit).  The draws'
+        moment vectors are built on the device.
+
+        Returns ``Delta`` and ``V`` [draws, H] (the mean and the variance of the
+        fleet's replacement count given the draw: the units are independent
+        then, so their variances add), ``nbad`` and ``nunits`` [draws],
+        ``words`` (int64 [draws, 2 H + 2]: exact integer sums, shards and ranks
+        add them, ``spares_combine``) with ``scales`` [draws, 2 H], ``dsum``,
+        ``vsum``, ``d2sum`` [units, H] and ``cnt`` [units] (the sums of D, of
+        the variance and of D^2 over the draws in which the unit was good, in
+        draw order, and their number), ``demand_unit`` = dsum / cnt and
+        ``demand_unit_sd`` = sqrt(vsum / cnt + d2sum / cnt - (dsum / cnt)^2)
+        (the posterior predictive mean and sd of each unit's count; NaN where
+        cnt is 0), ``unit_index``, ``bad_draw`` and ``flags``, and with
+        ``pointwise`` ``d`` and ``var`` [draws, units, H] (NaN where bad; for
+        tests and small fleets).  ``last_spares_ms`` then holds the device
+        time of the vectors and table kernels and of the unit kernel."""
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
+        h = np.ascontiguousarray(np.atleast_1d(horizons), np.float64).reshape(-1)
+        H = len(h)
+        idx = self.forecast_units()
+        nc = len(idx)
+        words, scales = np.zeros((nd, 2 * H + 2), np.int64), np.zeros((nd, 2 * H))
+        dsum, vsum, d2sum = np.zeros((nc, H)), np.zeros((nc, H)), np.zeros((nc, H))
+        cnt = np.zeros(nc, np.int64)
+        d = np.full((nd, nc, H), np.nan) if pointwise else None
+        var = np.full((nd, nc, H), np.nan) if pointwise else None
+        flags = np.zeros(nd, np.int32)
+        if self.L.pht_ctx_spares_grid_cap(self.ctx, int(grid_cap)) != 0:
+            raise _err(self.L)
+        if self.L.pht_ctx_spares(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), H, h if H else np.zeros(1),
+                                 int(batch), words.reshape(-1), scales.reshape(-1) if H else np.zeros(1),
+                                 dsum.ctypes.data, vsum.ctypes.data, d2sum.ctypes.data, cnt.ctypes.data,
+                                 d.ctypes.data if pointwise else None, var.ctypes.data if pointwise else None,
+                                 flags) != 0:
+            raise _err(self.L)
+        self.last_spares_ms = _ms_pair(self.L.pht_ctx_spares_ms, self.ctx)
+        return spares_finalise(words, scales, dsum, vsum, d2sum, cnt, idx, flags, d, var)
 
     def predict(self, S_list, s_list, nrep: int, key=(1, 2), rep0: int = 0, draw0: int = 0, edges=None,
                 horizon: float = np.inf, max_jumps=None, batch: int = 64, pointwise: bool = False):
@@ -1589,7 +1642,7 @@ def fleet_condition(res, x, TT_or_T, censored, horizons=None, C_=None, n=None, b
     ``*_band`` (the posterior ``band`` quantiles).  The demand of a draw is the
     MEAN of its replacement count: the variance of the count within a draw is
     not computed, so ``demand_sd`` is the spread between the draws only, a
-    LOWER bound of the predictive sd."""
+    LOWER bound of the predictive sd (``fleet_spares`` gives both parts)."""
     S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
     S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
     if not S_list:
@@ -1639,6 +1692,140 @@ def ph_mrl(S, s, given=0.0, device: int = 0):
     r, t = _condition_one(S, s, given, None, device)
     m = r["mrl"][0].reshape(t.shape)
     return float(m) if t.ndim == 0 else m
+
+
+# --------------------------------------------------------------- fleet spares
+# include/pht_spares.h, phasetype_amd/csrc/pht_spares.hip (no reference
+# counterpart): the variance of the replacement count beside its mean, and the
+# stock that covers the demand with a given probability
+def spares_finalise(words, scales, dsum, vsum, d2sum, cnt, unit_index, flags, d=None, var=None) -> dict:
+    """``Sweeper.spares``'s dict from the raw outputs (words int64 [draws,
+    2 H + 2], scales [draws, 2 H], dsum, vsum, d2sum [units, H], cnt [units],
+    the units' indices, the draws' flag words)."""
+    words = np.asarray(words, np.int64)
+    scales = np.asarray(scales, np.float64)
+    dsum, vsum, d2sum = np.asarray(dsum, np.float64), np.asarray(vsum, np.float64), np.asarray(d2sum, np.float64)
+    cnt = np.asarray(cnt, np.int64)
+    H = dsum.shape[1]
+    k = np.maximum(cnt, 1).astype(np.float64)[:, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        demand_unit = np.where(cnt[:, None] > 0, dsum / k, np.nan)
+        # the law of total variance per unit; a negative value is rounding alone
+        sd = np.sqrt(np.maximum(vsum / k + d2sum / k - (dsum / k) ** 2, 0.0))
+        demand_unit_sd = np.where(cnt[:, None] > 0, sd, np.nan)
+    flags = np.asarray(flags, np.int32)
+    out = dict(Delta=(words[:, :H] / CONDITION_SCALE) * scales[:, :H],
+               V=(words[:, H:2 * H] / CONDITION_SCALE) * scales[:, H:], nbad=words[:, 2 * H].copy(),
+               nunits=words[:, 2 * H + 1].copy(), words=words, scales=scales, dsum=dsum, vsum=vsum, d2sum=d2sum,
+               cnt=cnt, demand_unit=demand_unit, demand_unit_sd=demand_unit_sd,
+               unit_index=np.asarray(unit_index, np.int64), bad_draw=flags != 0, flags=flags)
+    if d is not None:
+        out.update(d=d, var=var)
+    return out
+
+
+def spares_host(S, s, ages, horizons, ymax_c: float = 0.0, state=None) -> dict:
+    """pht_spares_host (host only, no GPU): ``Sweeper.spares``'s dict for one
+    draw over units of the given ``ages``, with the pointwise values; bit for
+    bit what the device computes.  ``ymax_c``: the largest censored observation
+    the tables are sized for (0: the largest age).  ``state``: the dict of the
+    chain's earlier draws, whose per-unit sums and ``cnt`` this draw continues
+    (its words are not kept)."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    ages = np.ascontiguousarray(np.atleast_1d(ages), np.float64).reshape(-1)
+    h = np.ascontiguousarray(np.atleast_1d(horizons), np.float64).reshape(-1)
+    nc, H = len(ages), len(h)
+    words, scales = np.zeros((1, 2 * H + 2), np.int64), np.zeros((1, 2 * H))
+    if state is None:
+        dsum, vsum, d2sum, cnt = np.zeros((nc, H)), np.zeros((nc, H)), np.zeros((nc, H)), np.zeros(nc, np.int64)
+    else:
+        dsum, vsum = np.array(state["dsum"], np.float64), np.array(state["vsum"], np.float64)
+        d2sum, cnt = np.array(state["d2sum"], np.float64), np.array(state["cnt"], np.int64)
+        if dsum.shape != (nc, H) or vsum.shape != (nc, H) or d2sum.shape != (nc, H) or cnt.shape != (nc,):
+            raise ValueError("state does not have this call's units and horizons")
+    d, var = np.full((1, nc, H), np.nan), np.full((1, nc, H), np.nan)
+    f = L.pht_spares_host(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                          np.ascontiguousarray(s, np.float64).reshape(-1), nc, ages if nc else np.zeros(1), H,
+                          h if H else np.zeros(1), float(ymax_c), words.reshape(-1),
+                          scales.reshape(-1) if H else np.zeros(1), dsum.ctypes.data, vsum.ctypes.data,
+                          d2sum.ctypes.data, cnt.ctypes.data, d.ctypes.data, var.ctypes.data)
+    if f < 0:
+        raise _err(L)
+    return spares_finalise(words, scales, dsum, vsum, d2sum, cnt, np.arange(nc), np.array([f], np.int32), d, var)
+
+
+def spares_combine(a: dict, b: dict) -> dict:
+    """The spares of two shards' units from the spares of each
+    (``Sweeper.spares`` of the same draws and horizons on each shard): the
+    words add exactly (the scales depend on the draws alone; given the draw
+    the units are independent, so their variances add as their means do), the
+    per-unit blocks concatenate (``b``'s units after ``a``'s; ``unit_index``
+    stays each shard's own numbering)."""
+    if a["words"].shape != b["words"].shape or not np.array_equal(a["flags"], b["flags"]) \
+            or not np.array_equal(a["scales"], b["scales"]):
+        raise ValueError("the two spares results are not of the same draws and horizons")
+    pw = [np.concatenate([a[k], b[k]], axis=1) for k in ("d", "var")] if ("d" in a and "d" in b) else [None] * 2
+    return spares_finalise(a["words"] + b["words"], a["scales"], np.concatenate([a["dsum"], b["dsum"]]),
+                           np.concatenate([a["vsum"], b["vsum"]]), np.concatenate([a["d2sum"], b["d2sum"]]),
+                           np.concatenate([a["cnt"], b["cnt"]]),
+                           np.concatenate([a["unit_index"], b["unit_index"]]), a["flags"], *pw)
+
+
+def fleet_spares(res, x, TT_or_T, horizons, censored, C_=None, n=None, burn: int = 0, thin: int = 1,
+                 device: int = 0, batch: int = 64, collation: str = "C") -> dict:
+    """The spares a fleet needs from a chain (``res`` and ``TT_or_T`` as in
+    ``log_lik``; rows ``burn::thin``; the arguments of ``fleet_forecast``): of
+    the units of ``x`` still in service (``censored`` != 0, at age x_i), how
+    many failures occur within each of ``horizons`` when every failed unit is
+    replaced by a new one.  ``Sweeper.spares``'s dict plus, per horizon,
+    ``mean`` (the expected number, ``fleet_condition``'s ``demand_mean``),
+    ``sd`` (the predictive standard deviation by the law of total variance)
+    with its two parts ``within`` = mean_d V_d (the count's own randomness
+    given the parameters, which ``fleet_condition`` leaves out) and ``between``
+    = var_d Delta_d (the posterior's: ``fleet_condition``'s ``demand_sd``
+    squared), ``n_used`` (the draws that count: not flagged and with no bad
+    unit) and ``stock(p)``: the smallest whole number of spares whose
+    APPROXIMATE predictive probability of sufficing is at least p, the ceiling
+    of ``forecast_count_quantiles(Delta, V, p)`` (the equal-weight mixture over
+    the draws of normals matched to each draw's mean and variance; a count of
+    few failures is skewed and discrete, which a normal is not)."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    sw = _obs_sweeper(x, censored, n, device)
+    try:
+        r = sw.spares(S_list, s_list, horizons, batch=batch)
+    finally:
+        sw.close()
+    use = np.broadcast_to(((~r["bad_draw"]) & (r["nbad"] == 0))[:, None], r["Delta"].shape)
+    r.update(forecast_moments(r["Delta"], r["V"], use))
+    Delta, V = r["Delta"], r["V"]
+    r["use"] = use[:, 0].copy()
+    r["stock"] = lambda p: np.ceil(forecast_count_quantiles(Delta, V, p, use))
+    r["horizons"] = np.atleast_1d(np.asarray(horizons, np.float64))
+    return r
+
+
+def ph_renewal(S, s, h, given=0.0, device: int = 0):
+    """(mean, variance) of the number of failures within ``h`` of one unit of
+    age ``given`` (0: new) with law PH(e_1, S) that is replaced by a new one at
+    every failure; each the shape of ``h`` (increasing where it has several
+    values).  ``Sweeper.spares`` on one draw."""
+    S = np.asarray(S, np.float64)
+    hh = np.asarray(h, np.float64)
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        sw.set_obs(np.array([float(given)]), np.ones(1, np.int32))
+        r = sw.spares([S], [s], hh.reshape(-1), pointwise=True)
+    finally:
+        sw.close()
+    if r["bad_draw"][0]:
+        raise ValueError(f"not a usable generator (flag {r['flags'][0]})")
+    m, v = r["d"][0, 0].reshape(hh.shape), r["var"][0, 0].reshape(hh.shape)
+    return (float(m), float(v)) if hh.ndim == 0 else (m, v)
 
 
 # ------------------------------------------- expected statistics, EM fitting

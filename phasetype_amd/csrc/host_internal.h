@@ -19,6 +19,7 @@
  *   host_quantile.cpp  quantiles and residual-life quantiles: pht_ctx_quantile, pht_quantile_host
  *   host_forecast.cpp  fleet forecasts of the censored units: pht_ctx_forecast, pht_forecast_host
  *   host_condition.cpp fleet condition of the censored units: pht_ctx_condition, pht_condition_host
+ *   host_spares.cpp    fleet spares of the censored units: pht_ctx_spares, pht_spares_host
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -302,6 +303,17 @@ struct pht_ctx {
   DevBuf<unsigned long long> d_cdwords;
   int cd_grid_cap = 0;
   pht::host::PhaseClock cd_clk;
+  /* pht_ctx_spares (never the condition's buffers either): a call's horizons
+   * and Kr per draw, one batch's forward tables [draw][k][n], weights
+   * [draw][k][nh][T, p] and vectors [draw][r, q, scales], a call's words
+   * [draw][2 nh + 2], the units' sums [unit][3 nh + 1] and one batch's pointwise
+   * values [unit][draw][2 nh]; the units are obs.fc's (read only).  Default
+   * grid: two blocks a CU; clock: vectors with the tables, and units */
+  DevBuf<double> d_sph, d_spF, d_spW, d_spvec, d_spstate, d_sppw;
+  DevBuf<int> d_spkr;
+  DevBuf<unsigned long long> d_spwords;
+  int sp_grid_cap = 0;
+  pht::host::PhaseClock sp_clk;
 };
 
 namespace pht {
