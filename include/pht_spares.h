@@ -64,17 +64,27 @@
  * 1e-6 .. 1e3 / mu, margin four: these five sample the growth, they do not
  * bound it (pht_condition.h's method for PHT_CD_R_R).
  *   |q^_h[i] - q_h[i]| <= PHT_SP_Q_R (mu h + 8) q_h[i]          (pht_sp_q_bound)
- *     PHT_SP_Q_R = 3.2 x 2^-53; largest measured ratio 0.80 (bd_exit(10),
- *     mu h = 1e-3); at mu h = 1000 measured 4.4 .. 190 x 2^-53, stiff(6) the largest
+ *     PHT_SP_Q_R = 3.2 x 2^-53; largest measured ratio on the five 0.80
+ *     (bd_exit(10), mu h = 1e-3); at mu h = 1000 measured 4.4 .. 190 x 2^-53,
+ *     stiff(6) the largest
  *   a unit's variance loses what Q + D - D^2 cancels: with E = Q + D + D^2,
  *   |var^ - var| <= PHT_SP_V_R (mu h + 8) E + the error phi itself carries
  *     PHT_SP_V_R = 3.6 x 2^-53 (pht_sp_var_bound; the tests measure var with
- *     phi = e_i exact, i.e. on the columns: largest measured ratio 0.89, stiff(6),
- *     mu h = 1; at mu h = 1000 the error is 68 .. 281 x 2^-53 E, Erlang(3) the
- *     largest, where D = 334 and var loses 5.6e5 x 2^-53 of itself)
+ *     phi = e_i exact, i.e. on the columns: largest measured ratio on the five
+ *     0.89, stiff(6), mu h = 1; at mu h = 1000 the error is 68 .. 281 x 2^-53 E,
+ *     Erlang(3) the largest, where D = 334 and var loses 5.6e5 x 2^-53 of itself)
  *   so the relative error of var is about ulp (mu h) D^2 / var: a few digits
  *   are lost at D in the hundreds.
- * (tests/test_spares.py gates both on the same grid.)
+ * Measured since on ten more generators, the bidiagonal chains among them
+ * (acyclic, reversible, nearly equal, Erlang, shared-rate Coxian, gapped and
+ * hypoexponential at n = 6, hypoexp(10), acyclic(12), stiff(12); the truth at
+ * 60 + 6 n max(0, -log10(mu h)) + mu h / 2.3 digits, since q_h[i] is as small
+ * as (mu h)^(2 n - i) there): the constants hold, with less than the margin of
+ * four.  Largest measured ratio over all fifteen: q_h 2.81 (0.88 of the
+ * bound) and var 1.76 (0.49 of the bound), both hypoexp(10) at mu h = 0.1;
+ * hypoexp(6) 1.61 and gapped(6) 1.35 for q_h at mu h = 0.01; every other
+ * generator stays below 1.0 in both.
+ * (tests/test_spares.py gates both on the same grid, on all fifteen.)
  *
  * Exact reductions.  Per draw pht_sp_nwords(nh) = 2 nh + 2 int64 words over the
  * units good for that draw,

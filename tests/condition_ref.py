@@ -173,19 +173,40 @@ def truth_phi(S, ages):
     return out
 
 
-def truth_m(S):
-    """m = (-S)^-1 1 as mpmath numbers (60 digits)"""
+def truth_m(S, dps=60):
+    """m = (-S)^-1 1 as mpmath numbers.  Every m_i is a mean time to absorption,
+    at least 1 / mu, and the solve's error is relative to the largest of them
+    times the condition number: 60 digits, with the residual checked to 30
+    digits below the smallest m_i"""
     import mpmath as mp
 
-    with mp.workdps(60):
+    with mp.workdps(dps):
         A = -mp.matrix(np.asarray(S, np.float64).tolist())
-        return list(mp.lu_solve(A, mp.ones(A.rows, 1)))
+        one = mp.ones(A.rows, 1)
+        m = mp.lu_solve(A, one)
+        res = mp.norm(A * m - one, mp.inf)
+        amax = max(mp.fabs(A[i, j]) for i in range(A.rows) for j in range(A.cols))
+        assert min(m) > 0 and res <= mp.mpf(10) ** (30 - dps) * amax * min(m), \
+            ("the working precision does not resolve m", dps, float(res))
+        return list(m)
 
 
-def truth_r(S, s, horizons):
+def truth_r_dps(n, x):
+    """the working precision of truth_r at x = mu h: r_h[i] is as small as
+    (mu h)^(n - i) on a chain and expm's error is absolute, so
+    60 + ceil(3 n max(0, -log10 x)) + x / 2.3 digits (evaluator_cases._dps's
+    growth)"""
+    import math
+
+    small = math.ceil(3 * n * max(0.0, -math.log10(x))) if x > 0 else 0
+    return int(60 + small + int(x / 2.3))
+
+
+def truth_r(S, s, horizons, dps=None):
     """r_h[i] = (int_0^h exp(Q* u) s du)_i, Q* = S + s e_1^T, as mpmath numbers:
-    the last column of exp([[Q*, s], [0, 0]] h) (60 digits and more for a long
-    horizon)"""
+    the last column of exp([[Q*, s], [0, 0]] h), at truth_r_dps digits (dps: a
+    fixed precision instead, for the test of the guard); a value that the
+    working precision does not resolve by 30 digits fails here"""
     import mpmath as mp
 
     S = np.asarray(S, np.float64)
@@ -193,7 +214,8 @@ def truth_r(S, s, horizons):
     mu = float(np.max(-np.diag(S)))
     out = []
     for h in horizons:
-        with mp.workdps(60 + int(mu * float(h) / 2.3)):
+        wp = truth_r_dps(n, mu * float(h)) if dps is None else int(dps)
+        with mp.workdps(wp):
             M = mp.zeros(n + 1, n + 1)
             for i in range(n):
                 for j in range(n):
@@ -202,6 +224,9 @@ def truth_r(S, s, horizons):
                 M[i, n] = mp.mpf(float(s[i]))
             E = mp.expm(M * mp.mpf(float(h)))
             out.append([E[i, n] for i in range(n)])
+            if float(h) > 0:
+                assert all(v > mp.mpf(10) ** (30 - wp) for v in out[-1]), \
+                    ("the working precision does not resolve this r_h", float(h), wp, float(min(out[-1])))
     return out
 
 

@@ -1,8 +1,11 @@
 """The generators, observations and mpmath truth on which both log-likelihood
 evaluators (include/pht_loglik.h, include/pht_loglik_unif.h) are tested off
 BD-exit.  Shared by tests/test_loglik.py, test_loglik_unif.py, test_estep.py,
-test_quantile.py and the GPU tests of the two kernels.  CPU only: no GPU and no
-oracle is in it.
+test_quantile.py and the GPU tests of the two kernels; OFF_BD_GPU, fleet and
+horizons are the cases and shapes on which the GPU tests of the six
+post-processing kernels run the same families, TRUTH_CASES the generators that
+test_condition.py, test_spares.py and test_forecast.py add to their own.  CPU
+only: no GPU and no oracle is in it.
 
 Families, each (S, s) with pi = e_1:
 
@@ -107,6 +110,19 @@ CASES = ([("bd", n, {}) for n in NEW_N]
 # one per family for the kernels' bit-exactness (n in NEW_N there, set by the test)
 FAMILIES = ("bd", "acyclic", "reversible", "neareq", "stiff", "erlang", "coxian_shared", "gapped", "hypoexp")
 
+# the cases on which the six post-processing kernels (E-step, quantile,
+# forecast, condition, spares, predict) run off BD-exit on the GPU: every
+# family; n = 3 and 10 take the kernels' compile-time builds, n = 6 and 12 the
+# runtime-n ones, and neither of the latter divides the wave
+OFF_BD_GPU = ([(f, n, {}) for f in ("acyclic", "reversible", "neareq", "stiff") for n in STRUCT_N]
+              + [(f, n, {"eps": 1e-3} if f == "gapped" else {})
+                 for f in ("bd", "erlang", "coxian_shared", "gapped", "hypoexp") for n in (3, 10)])
+assert len(OFF_BD_GPU) == 18 and {c[0] for c in OFF_BD_GPU} == set(FAMILIES)
+DRAW_SCALE = 1.25  # the largest scaling of loglik_unif_ref.SCALES, the five draws of every such test
+MU_C_MAX = 1000.0  # the documented limit of an age (README): mu c <= 1000
+HORIZON_GRID = (0.0, 1e-9, 1e-3, 0.1, 1.0, 10.0)
+QUANTILE_P = (1e-6, 1e-3, 0.1, 0.5, 0.9, 1 - 1e-9)
+
 
 # -------------------------------------------------------------- observations
 def observations(S, scale=1.0):
@@ -125,6 +141,42 @@ def tiled(y, cens, N):
     order = np.arange(2 * k).reshape(2, k).T.reshape(-1)  # exact y0, censored y0, exact y1, ...
     idx = order[np.arange(N) % (2 * k)]
     return np.ascontiguousarray(y[idx]), np.ascontiguousarray(cens[idx].astype(np.int32))
+
+
+# the generators on which tests/test_condition.py, test_spares.py and
+# test_forecast.py hold their restatements to the truth, beyond their own five
+TRUTH_CASES = {family + str(n): (lambda family=family, n=n, kw=kw: generator(family, n, **kw))
+               for family, n, kw in [("acyclic", 6, {}), ("reversible", 6, {}), ("neareq", 6, {}), ("erlang", 6, {}),
+                                     ("coxian_shared", 6, {}), ("gapped", 6, {"eps": 1e-9}), ("hypoexp", 6, {}),
+                                     ("hypoexp", 10, {}), ("acyclic", 12, {}), ("stiff", 12, {})]}
+
+
+def fleet(S, scale=DRAW_SCALE, units=65):
+    """(y, cens) of a fleet: the ages of Y_GRID with scale mu c <= MU_C_MAX,
+    tiled to ``units`` censored units with as many exact observations
+    interleaved (exact y0, censored y0, exact y1, ...: ties among the ages and
+    between an exact and a censored observation come from the tiling)"""
+    mu = float(np.max(-np.diag(S))) * scale
+    ages = [c for c in Y_GRID if mu * c <= MU_C_MAX]
+    k = len(ages)
+    y = np.array(ages + ages)
+    cens = np.concatenate([np.zeros(k, np.int32), np.ones(k, np.int32)])
+    return tiled(y, cens, 2 * units)
+
+
+def horizons(S, scale, c_max):
+    """HORIZON_GRID without the h with scale mu (c_max + h) > MU_Y_MAX"""
+    mu = float(np.max(-np.diag(S))) * scale
+    return np.array([h for h in HORIZON_GRID if mu * (float(c_max) + h) <= MU_Y_MAX])
+
+
+def off_bd_case(case, units=65):
+    """(S, s, y, cens, h) of one case of OFF_BD_GPU: the generator, its fleet
+    and the horizons for the largest draw (DRAW_SCALE) and the largest age"""
+    family, n, kw = case
+    S, s = generator(family, n, **kw)
+    y, cens = fleet(S, DRAW_SCALE, units)
+    return S, s, y, cens, horizons(S, DRAW_SCALE, float(np.max(y[cens != 0])))
 
 
 # --------------------------------------------------------------------- truth

@@ -137,11 +137,24 @@ def same_bits(a, b, keys=ALL):
 
 
 # --------------------------------------------------------------------- truth
-def truth_moments(S, s, horizons):
+def truth_dps(n, x):
+    """the working precision of truth_moments at x = mu h:
+    60 + ceil(6 n max(0, -log10 x)) + x / 2.3 digits"""
+    import math
+
+    small = math.ceil(6 * n * max(0.0, -math.log10(x))) if x > 0 else 0
+    return int(60 + small + int(x / 2.3))
+
+
+def truth_moments(S, s, horizons, dps=None):
     """(M1, M2) per horizon as lists of mpmath numbers per phase: M1 = E_i N(h),
     M2 = E_i N(h) (N(h) - 1), the last column of exp(G h),
-    G = [[Q*, 2 s e_1^T, 0], [0, Q*, s], [0, 0, 0]], Q* = S + s e_1^T (60 digits
-    and more for a long horizon)"""
+    G = [[Q*, 2 s e_1^T, 0], [0, Q*, s], [0, 0, 0]], Q* = S + s e_1^T.  expm's
+    error is absolute and on a chain M2[i] is as small as (mu h)^(2 n - i), so
+    the digits grow with n and -log10(mu h) as evaluator_cases._dps grows them
+    (over the 2 n transient states of G), and with mu h (dps: a fixed precision
+    instead, for the test of the guard); a value that the working precision
+    does not resolve by 30 digits fails here"""
     import mpmath as mp
 
     S = np.asarray(S, np.float64)
@@ -149,7 +162,8 @@ def truth_moments(S, s, horizons):
     mu = float(np.max(-np.diag(S)))
     m1, m2 = [], []
     for h in horizons:
-        with mp.workdps(60 + int(mu * float(h) / 2.3)):
+        wp = truth_dps(n, mu * float(h)) if dps is None else int(dps)
+        with mp.workdps(wp):
             G = mp.zeros(2 * n + 1, 2 * n + 1)
             for i in range(n):
                 for j in range(n):
@@ -162,4 +176,8 @@ def truth_moments(S, s, horizons):
             E = mp.expm(G * mp.mpf(float(h)))
             m2.append([E[i, 2 * n] for i in range(n)])
             m1.append([E[n + i, 2 * n] for i in range(n)])
+            if float(h) > 0:
+                low = mp.mpf(10) ** (30 - wp)
+                assert all(v > low for v in m1[-1] + m2[-1]), \
+                    ("the working precision does not resolve this moment", float(h), wp, float(min(m1[-1] + m2[-1])))
     return m1, m2

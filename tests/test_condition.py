@@ -33,6 +33,7 @@ CASES = {
     "ring5": lambda: U.ring(5),
     "stiff6": lambda: EC.stiff(6),
 }
+CASES.update(EC.TRUTH_CASES)  # the chain families, the structures and a stiffer table (evaluator_cases)
 AGES = np.array([1e-6, 1e-3, 0.1, 1.0, 5.0, 20.0])
 HORIZONS = np.array([0.0, 1e-9, 0.1, 1.0, 10.0])
 ULP = 2.0 ** -53
@@ -102,6 +103,27 @@ def test_m_and_r_within_the_recorded_constants(name):
     print(f"{name}: m error {em / ULP:.2f} x 2^-53 (recorded {Cd.spec().cspec_m_r() / ULP:.0f}), "
           f"r error / recorded bound {worst:.3f}")
     assert em <= Cd.spec().cspec_m_r()
+
+
+def test_truth_is_resolved_or_refused():
+    """Erlang(10) at mu h = 1e-6: r_h[0] = x^10 / 10! (1 + O(x)) = 3e-67.  At a
+    fixed 60 digits the helper must refuse; at its own precision it gives the
+    closed form's leading term.  m of the same chain is (n - i) / lam"""
+    import mpmath as mp
+
+    n, x = 10, 1e-6
+    S, s = EC.erlang(n)
+    h = [x / _mu(S)]
+    with pytest.raises(AssertionError, match="does not resolve"):
+        Cd.truth_r(S, s, h, dps=60)
+    assert Cd.truth_r_dps(n, x) == 60 + 3 * n * 6
+    r = Cd.truth_r(S, s, h)
+    with mp.workdps(60):
+        xm = mp.mpf(_mu(S)) * mp.mpf(h[0])
+        assert abs(r[0][0] / (xm ** n / mp.factorial(n)) - 1) < 2 * x
+        assert abs(r[0][n - 1] / xm - 1) < 2 * x
+        m = Cd.truth_m(S)
+        assert all(abs(m[i] * mp.mpf(EC.LAM) / (n - i) - 1) < mp.mpf(10) ** -50 for i in range(n))
 
 
 def test_issue_orientation_values():

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import condition_ref as Cd  # noqa: E402
+import evaluator_cases as EC  # noqa: E402
 import forecast_ref as F  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -86,6 +87,79 @@ def test_bit_equal_to_the_restatement(gpu, units, nd, batch, H, gen):
     assert np.all(np.isfinite(got["phi"])) and np.all(np.isfinite(got["mrl"])) and np.all(np.isfinite(got["d"]))
     assert np.all(got["cnt"] == nd) and np.all(got["nunits"] == units) and not got["flags"].any()
     assert np.array_equal(got["unit_index"], np.flatnonzero(cens))
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = P.Sweeper(n, ECS, 1, device=0)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+def _clean(r):
+    """no draw flagged, no unit bad, every value finite"""
+    assert not r["flags"].any() and not r["bad_draw"].any() and not r["nbad"].any()
+    for k in POINTS:
+        assert np.all(np.isfinite(r[k])), k
+
+
+POINTS = Cd.POINT + ("Phi", "L", "Delta", "p_phase", "mrl_unit", "demand_unit", "phisum", "mrlsum", "dsum", "scales")
+TRUTH_ON_GPU = ("hypoexp-10", "stiff-12")
+
+
+def _phi_within_contract(S, s, y, cens, phi):
+    """phi [units, n] of the draw (S, s) against the truth at every distinct
+    age, within the header's contract (as tests/test_condition.py holds the
+    restatement to it); the largest error / bound"""
+    import mpmath as mp
+
+    n = S.shape[0]
+    _, ages = Cd.units(y, cens)
+    first = np.unique(ages, return_index=True)[1]
+    _, bad, khi = Cd.windows(S, s, ages[first], ymax_c=float(np.max(ages)))
+    assert not bad.any()
+    truth = Cd.truth_phi(S, ages[first])
+    worst = 0.0
+    for i, u in enumerate(first):
+        for j in range(n):
+            b = Cd.spec().cspec_phi_bound(n, int(khi[i]), float(truth[i][j]))
+            e = float(abs(mp.mpf(float(phi[u, j])) - truth[i][j]))
+            worst = max(worst, e / b)
+            assert e <= b, (ages[u], j, e, b)
+    return worst
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py: single-successor rows, exact
+    zeros in the forward vectors and in phi, a shift for R (Erlang), rates over
+    four decades (stiff); 5 draws, 65 units among 130 observations with ties,
+    the horizons within the tables; batch 64 and 2.  On hypoexp10 and stiff12
+    the kernel's own phi is held to the truth as well."""
+    S, s, y, cens, h = EC.off_bd_case(case)
+    n = S.shape[0]
+    Ss, ss = U.scaled(S, s)
+    want = Cd.condition(Ss, ss, y, cens, h)
+    _clean(want)
+    assert want["phi"].shape == (5, 65, n) and np.all(want["cnt"] == 5) and np.all(want["nunits"] == 65)
+    sw = sweepers(n)
+    sw.set_obs(y, cens)
+    for batch in (64, 2):
+        got = sw.condition(Ss, ss, h, batch=batch, pointwise=True)
+        _clean(got)
+        assert Cd.same_bits(got, want, ALL) == [], batch
+    print(f"{EC.case_id(case)}: exact zeros in phi {int((got['phi'] == 0).sum())} of {got['phi'].size}")
+    if EC.case_id(case) in TRUTH_ON_GPU:
+        worst = _phi_within_contract(Ss[2], ss[2], y, cens, got["phi"][2])
+        print(f"{EC.case_id(case)}: the kernel's phi, largest error / bound {worst:.4f}")
 
 
 def test_table_sizes_mixed_in_one_call(gpu):

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import estep_ref as R  # noqa: E402
+import evaluator_cases as EC  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
 from phasetype_amd.synth import bd_exit, simulate_ph  # noqa: E402
@@ -86,6 +87,48 @@ def test_bit_equal_to_the_restatement(gpu, n, N, nd):
     sw.close()
     assert got["yscale"] == want[0]["yscale"]
     _check(got, want, (n, N, nd))
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = P.Sweeper(n, ECS, 1, device=0)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py through the histogram and the
+    contraction: rows of R with one non-zero, forward vectors with exact
+    zeros, a shift for R (Erlang), rates over four decades (stiff).  5 draws,
+    130 observations (the grid of y, each exact and censored, tiled; ties),
+    batch 64 and 2; no draw flagged, no observation bad, every value finite,
+    in the restatement and on the GPU."""
+    family, n, kw = case
+    S, s = EC.generator(family, n, **kw)
+    Ss, ss = U.scaled(S, s)
+    y, cens = EC.tiled(*EC.observations(S, scale=EC.DRAW_SCALE), 130)
+    want = _want(Ss, ss, y, cens)
+    for w in want:
+        assert w["flag"] == 0 and w["nbad"] == 0 and int(w["totals"][3]) == 130 and np.isfinite(w["loglik"])
+        assert all(np.all(np.isfinite(w[k])) for k in KEYS)
+    sw = sweepers(n)
+    sw.set_obs(y, cens)
+    for batch in (64, 2):
+        got = sw.estep(Ss, ss, batch=batch)
+        assert got["yscale"] == want[0]["yscale"]
+        assert not np.asarray(got["flags"]).any() and not np.asarray(got["nbad"]).any()
+        assert np.all(np.asarray(got["nobs"]) == 130) and np.all(np.isfinite(got["loglik"]))
+        assert all(np.all(np.isfinite(got[k])) for k in KEYS)
+        _check(got, want, (EC.case_id(case), batch))
 
 
 @pytest.fixture(scope="module")

@@ -13,6 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import forecast_ref as F  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -80,6 +81,74 @@ def test_bit_equal_to_the_restatement(gpu, units, nd, batch, H, gen):
     assert got["q"].shape == (nd, units, H) and np.all(np.isfinite(got["q"]))
     assert np.all(got["cnt"] == nd) and np.all(got["nunits"] == units)
     assert np.array_equal(got["unit_index"], np.flatnonzero(cens))
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = P.Sweeper(n, ECS, 1, device=0)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+TRUTH_ON_GPU = ("hypoexp-10", "stiff-12")
+
+
+def _clean(r):
+    """no draw flagged, no unit bad at any horizon, every value finite"""
+    assert not r["flags"].any() and not r["bad_draw"].any() and not r["nbad"].any()
+    for k in ("q", "M", "V", "p_unit", "qsum"):
+        assert np.all(np.isfinite(r[k])), k
+
+
+def _q_within_contract(S, s, y, cens, h, q):
+    """q [units, H] of the draw (S, s) against the truth at every distinct age,
+    within the header's contract from the context's table (as
+    tests/test_forecast.py holds the restatement to it); the largest
+    error / bound"""
+    _, ages = F.units(y, cens)
+    first = np.unique(ages, return_index=True)[1]
+    truth = F.truth(S, s, ages[first], h)
+    B = F.bound(S, s, ages[first], h, truth, ymax_c=float(np.max(ages)), hmax=float(h[-1]))
+    worst = 0.0
+    for i, u in enumerate(first):
+        for j in range(len(h)):
+            err = float(abs(truth[i][j] - float(q[u, j])))
+            assert err <= B[i, j], (ages[u], h[j], err, B[i, j])
+            if B[i, j] > 0:
+                worst = max(worst, err / B[i, j])
+    return worst
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py (single-successor rows, exact
+    zeros in the forward vectors, a shift for R, rates over four decades):
+    5 draws, 65 units among 130 observations with ties, the horizons within
+    the table; batch 64 and 2.  On hypoexp10 and stiff12 the kernel's own q is
+    held to the truth as well."""
+    S, s, y, cens, h = EC.off_bd_case(case)
+    Ss, ss = U.scaled(S, s)
+    want = F.forecast(Ss, ss, y, cens, h)
+    _clean(want)
+    assert want["q"].shape == (5, 65, len(h)) and np.all(want["cnt"] == 5) and np.all(want["nunits"] == 65)
+    sw = sweepers(S.shape[0])
+    sw.set_obs(y, cens)
+    for batch in (64, 2):
+        got = sw.forecast(Ss, ss, h, batch=batch, pointwise=True)
+        _clean(got)
+        assert F.same_bits(got, want, ALL) == [], batch
+        assert not got["q"][:, :, 0].any()  # h = 0
+    if EC.case_id(case) in TRUTH_ON_GPU:
+        worst = _q_within_contract(Ss[2], ss[2], y, cens, h, got["q"][2])
+        print(f"{EC.case_id(case)}: the kernel's q, largest error / contract {worst:.4f}")
 
 
 def test_table_sizes_mixed_in_one_call(gpu):

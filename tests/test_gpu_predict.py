@@ -13,6 +13,8 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
+import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
 import predict_ref as R  # noqa: E402
 from phasetype_amd.synth import bd_exit_structure, simulate_ph  # noqa: E402
@@ -50,6 +52,51 @@ def test_pointwise_bit_exact(gpu, n):
     assert "y" not in totals
     R.assert_same(totals, want, pointwise=False)
     assert np.array_equal(R.bits(got["mean"]), R.bits(want["mean"])) and np.array_equal(got["ecdf"], want["ecdf"])
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = _sweeper(n)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+def _paths_clean(r):
+    """no draw flagged, no replicate bad, every value finite"""
+    assert not np.asarray(r["flags"]).any() and not np.asarray(r["nbad"]).any() and np.all(r["ndone"] == 257)
+    assert np.all(np.isfinite(r["y"])) and np.all(r["y"] > 0) and np.all(r["jumps"] >= 1)
+    assert np.all(np.isfinite(r["ymin"])) and np.all(np.isfinite(r["ymax"])) and np.all(np.isfinite(r["mean"]))
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py through the jump selection:
+    rows with a single successor (the chain families: every jump probability 0
+    or 1 but for coxian_shared's exits), exit rates of exactly 0, holding rates
+    over four decades (stiff).  5 draws, 257 replicates, 16 edges at
+    0.1 .. 3 x the mean; batch 64 and 2."""
+    family, n, kw = case
+    S, s = EC.generator(family, n, **kw)
+    Ss, ss = U.scaled(S, s)
+    edges = np.linspace(0.1, 3.0, 16) * R.moments(S)[0]
+    want = R.predict(Ss, ss, 257, edges=edges)
+    _paths_clean(want)
+    if family in ("erlang", "gapped", "hypoexp"):  # one way through the chain
+        assert np.all(want["jumps"] == n)
+    sw = sweepers(n)
+    for batch in (64, 2):
+        got = sw.predict(Ss, ss, 257, key=R.KEY, edges=edges, batch=batch, pointwise=True)
+        _paths_clean(got)
+        R.assert_same(got, want)
+        assert np.array_equal(R.bits(got["mean"]), R.bits(want["mean"])) and np.array_equal(got["ecdf"], want["ecdf"])
 
 
 @pytest.fixture(scope="module")

@@ -12,6 +12,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import evaluator_cases as EC  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import quantile_ref as Q  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -92,6 +93,62 @@ def test_bit_equal_to_the_restatement(gpu, n, nd, P_, batch, given, tmax):
     got = sw.quantile(Ss, ss, probs, given=given, tmax=tmax, batch=batch)
     sw.close()
     _check(got, want, (n, nd, P_, batch, given, tmax))
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = P.Sweeper(n, ECS, 1, device=0)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+def _roots_clean(r, family):
+    """no draw flagged, every root found and finite.  On ``stiff`` the slowest
+    phases put the upper quantiles beyond the table's horizon, as
+    tests/test_quantile.py documents: PHT_Q_F_BEYOND and no other flag, and at
+    least 10 of the 30 roots finite"""
+    assert not r["bad_draw"].any() and not r["draw_flags"].any()
+    assert r["t"].shape == (5, len(EC.QUANTILE_P)) and np.all(r["nev"] >= 1)
+    if family == "stiff":
+        assert set(np.unique(r["flags"]).tolist()) <= {0, Q.F_BEYOND}
+        assert np.isfinite(r["t"]).sum() >= 10
+    else:
+        assert not r["flags"].any() and np.all(np.isfinite(r["t"]))
+    ok = r["flags"] == 0
+    assert np.all(np.isfinite(r["t"][ok])) and np.all(r["t"][ok] > 0) and np.all(np.isinf(r["t"][~ok]))
+    assert np.all(np.isfinite(r["lo"][ok])) and np.all(np.isfinite(r["hi"][ok]))
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py through the bracketed Newton
+    lanes: f(t) ~ t^(n - 1) at the lower quantiles of the chain families (up
+    to 98 evaluations a root on Erlang(3)), a shift for R, rates over four
+    decades.
+    5 draws, the probabilities 1e-6 .. 1 - 1e-9, unconditional and given
+    survival to the fleet's second-largest age; batch 64 and 2."""
+    S, s, y, cens, _ = EC.off_bd_case(case)
+    n = S.shape[0]
+    Ss, ss = U.scaled(S, s)
+    probs = np.array(EC.QUANTILE_P)
+    given = float(np.unique(y[cens != 0])[-2])
+    sw = sweepers(n)
+    for g in (0.0, given):
+        want = Q.quantile(Ss, ss, probs, given=g)
+        _roots_clean(want, case[0])
+        assert want["nev"].max() < Q.spec().qspec_maxit()
+        for batch in (64, 2):
+            got = sw.quantile(Ss, ss, probs, given=g, batch=batch)
+            _roots_clean(got, case[0])
+            _check(got, want, (EC.case_id(case), g, batch))
 
 
 @pytest.fixture(scope="module")

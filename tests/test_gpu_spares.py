@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import condition_ref as Cd  # noqa: E402
+import evaluator_cases as EC  # noqa: E402
 import forecast_ref as F  # noqa: E402
 import loglik_unif_ref as U  # noqa: E402
 import phasetype_amd as P  # noqa: E402
@@ -104,6 +105,97 @@ def test_agrees_with_the_condition(gpu, units, nd, batch, H, gen):
         assert np.ascontiguousarray(got[k]).tobytes() == np.ascontiguousarray(cond[k]).tobytes(), k
     assert np.array_equal(got["words"][:, :H], cond["words"][:, n + 1:n + 1 + H])
     assert np.array_equal(got["scales"][:, :H], cond["scales"][:, 1:])
+
+
+@pytest.fixture(scope="module")
+def sweepers(gpu):
+    """one context per n for the cases of evaluator_cases.OFF_BD_GPU"""
+    held = {}
+
+    def get(n):
+        if n not in held:
+            held[n] = P.Sweeper(n, ECS, 1, device=0)
+        return held[n]
+
+    yield get
+    for sw in held.values():
+        sw.close()
+
+
+POINTS = Sp.POINT + ("Delta", "V", "demand_unit", "demand_unit_sd", "dsum", "vsum", "d2sum", "scales")
+TRUTH_ON_GPU = ("hypoexp-10", "stiff-12")
+
+
+def _clean(r):
+    """no draw flagged, no unit bad, every value finite"""
+    assert not r["flags"].any() and not r["bad_draw"].any() and not r["nbad"].any()
+    for k in POINTS:
+        assert np.all(np.isfinite(r[k])), k
+
+
+def _var_within_contract(S, s, y, cens, h, d, var):
+    """d, var [units, H] of the draw (S, s) against the truth at every distinct
+    age, within the recorded constants on top of phi's contract and the dots'
+    roundings (the tolerance of tests/test_spares.py's
+    test_a_units_var_within_the_constants_and_phis_contract); the largest
+    error / tolerance of var"""
+    import mpmath as mp
+
+    n, mu = S.shape[0], float(np.max(-np.diag(S)))
+    _, ages = Sp.units(y, cens)
+    first = np.unique(ages, return_index=True)[1]
+    _, bad, khi = Cd.windows(S, s, ages[first], ymax_c=float(np.max(ages)))
+    assert not bad.any()
+    phi = Cd.truth_phi(S, ages[first])
+    m1, m2 = Sp.truth_moments(S, s, h)
+    worst = 0.0
+    for i, u in enumerate(first):
+        pb = [Cd.spec().cspec_phi_bound(n, int(khi[i]), float(phi[i][k])) for k in range(n)]
+        for j, hj in enumerate(h):
+            D = mp.fsum(p * a for p, a in zip(phi[i], m1[j]))
+            Q = mp.fsum(p * a for p, a in zip(phi[i], m2[j]))
+            vt = Q + D - D * D
+            Df, Qf = float(D), float(Q)
+            tol = Sp.spec().sspec_var_bound(mu * hj, Df, Qf) + (n + 2) * ULP * (Qf + Df + 2 * Df * Df) + \
+                sum(pb[k] * float(m2[j][k] + m1[j][k] + 2 * D * m1[j][k]) for k in range(n))
+            e = float(abs(mp.mpf(float(var[u, j])) - vt))
+            assert e <= tol, (ages[u], hj, e, tol)
+            if tol > 0:
+                worst = max(worst, e / tol)
+            assert abs(d[u, j] - Df) <= (Cd.spec().cspec_r_bound(mu * hj) + (n + 2) * ULP) * Df + \
+                sum(pb[k] * float(m1[j][k]) for k in range(n)), (ages[u], hj)
+    return worst
+
+
+@pytest.mark.parametrize("case", EC.OFF_BD_GPU, ids=EC.case_id)
+def test_off_bd_exit_bit_equal_to_the_restatement(gpu, sweepers, case):
+    """The families of tests/evaluator_cases.py (single-successor rows, exact
+    zeros in phi, a shift for R, rates over four decades) through the
+    device-built r_h / q_h recurrences: 5 draws, 65 units among 130
+    observations with ties, the horizons within the tables; batch 64 and 2;
+    d is the condition's bit for bit.  On hypoexp10 and stiff12 the kernel's
+    own var and d are held to the truth as well."""
+    S, s, y, cens, h = EC.off_bd_case(case)
+    n, H = S.shape[0], len(h)
+    Ss, ss = U.scaled(S, s)
+    want = Sp.spares(Ss, ss, y, cens, h)
+    _clean(want)
+    assert want["var"].shape == (5, 65, H) and np.all(want["cnt"] == 5) and np.all(want["nunits"] == 65)
+    sw = sweepers(n)
+    sw.set_obs(y, cens)
+    for batch in (64, 2):
+        got = sw.spares(Ss, ss, h, batch=batch, pointwise=True)
+        _clean(got)
+        assert Sp.same_bits(got, want) == [], batch
+        assert np.all(got["var"] >= 0) and not got["d"][:, :, 0].any() and not got["var"][:, :, 0].any()  # h = 0
+        cond = sw.condition(Ss, ss, h, batch=batch, pointwise=True)
+        for k in ("d", "dsum", "Delta", "flags", "cnt", "nbad", "nunits", "demand_unit"):
+            assert np.ascontiguousarray(got[k]).tobytes() == np.ascontiguousarray(cond[k]).tobytes(), (k, batch)
+        assert np.array_equal(got["words"][:, :H], cond["words"][:, n + 1:n + 1 + H])
+        assert np.array_equal(got["scales"][:, :H], cond["scales"][:, 1:])
+    if EC.case_id(case) in TRUTH_ON_GPU:
+        worst = _var_within_contract(Ss[2], ss[2], y, cens, h, got["d"][2], got["var"][2])
+        print(f"{EC.case_id(case)}: the kernel's var, largest error / tolerance {worst:.4f}")
 
 
 def test_table_sizes_mixed_in_one_batch(gpu):

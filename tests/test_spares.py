@@ -32,6 +32,7 @@ CASES = {
     "ring5": lambda: U.ring(5),
     "stiff6": lambda: EC.stiff(6),
 }
+CASES.update(EC.TRUTH_CASES)  # the chain families, the structures and a stiffer table (evaluator_cases)
 HORIZONS = np.array([0.0, 1e-9, 0.1, 1.0, 10.0])
 ULP = 2.0 ** -53
 
@@ -98,6 +99,26 @@ def test_q_and_var_within_the_recorded_constants(name):
             assert ev <= bv, (name, hj, i, ev, bv)
     print(f"{name}: q error / recorded bound {wq:.3f}, var error / recorded bound {wv:.3f}, "
           f"largest relative error of var {lost / ULP:.3g} x 2^-53")
+
+
+def test_truth_is_resolved_or_refused():
+    """Erlang(10) at mu h = 1e-5: q_h[0] = 2 x^20 / 20! (1 + O(x)) = 8e-119.  At
+    a fixed 60 digits the helper must refuse; at its own precision it gives
+    the closed form's leading term"""
+    import mpmath as mp
+
+    n, x = 10, 1e-5
+    S, s = EC.erlang(n)
+    h = [x / _mu(S)]
+    with pytest.raises(AssertionError, match="does not resolve"):
+        Sp.truth_moments(S, s, h, dps=60)
+    assert Sp.truth_dps(n, x) == 60 + 6 * n * 5
+    m1, m2 = Sp.truth_moments(S, s, h)
+    with mp.workdps(60):
+        xm = mp.mpf(_mu(S)) * mp.mpf(h[0])
+        assert abs(m2[0][0] / (2 * xm ** (2 * n) / mp.factorial(2 * n)) - 1) < 2 * x
+        assert abs(m1[0][0] / (xm ** n / mp.factorial(n)) - 1) < 2 * x
+        assert abs(m1[0][n - 1] / xm - 1) < 2 * x
 
 
 @pytest.mark.parametrize("name", ["bd3", "ring5"])
