@@ -8,7 +8,8 @@ pht_loglik_unif.hip by uniformisation) and the posterior-predictive kernel
 (pht_predict.hip), the PSIS-LOO kernels (pht_psis.hip), the E-step kernels
 (pht_estep.hip), the quantile kernel (pht_quantile.hip), the forecast
 kernel (pht_forecast.hip), the condition kernels (pht_condition.hip) and the
-spares kernels (pht_spares.hip), then one link.
+spares kernels (pht_spares.hip), then one link.  The walk over passes, tiles
+and draws that four of them share is pht_unit_walk.h, the wave sum pht_wave.h.
 ``-ffp-contract=off`` is required: the device path must reproduce the
 oracle's arithmetic bit for bit (no implicit FMA contraction anywhere).
 """
@@ -43,7 +44,7 @@ UNIT_DEFINES = {5: ("PHT_PHILOX_UNROLL",), 20: ("PHT_PHILOX_UNROLL",),
 # the host runtime, one job per unit (csrc/host_internal.h lists them)
 HOST_UNITS = ("host_r.cpp", "host_params.cpp", "host_ctx.cpp", "host_chains.cpp", "host_rccl.cpp", "host_gibbs.cpp",
               "host_resident.cpp", "host_unif.cpp", "host_loglik.cpp", "host_predict.cpp", "host_psis.cpp", "host_estep.cpp", "host_quantile.cpp",
-              "host_forecast.cpp", "host_condition.cpp", "host_spares.cpp")
+              "host_fleet.cpp", "host_forecast.cpp", "host_condition.cpp", "host_spares.cpp")
 # (source, extra defines, extra device-compile flags) per object; the kernel
 # units first: the long compiles start first
 UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT_FLAGS.get(k, ()))
@@ -76,7 +77,7 @@ HEADERS = ["pht_claim.h", "pht_device.h", "pht_env.h", "pht_kernels.h", "pht_ker
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
            "pht_loglik_args.h", "pht_loglik_unif_args.h", "pht_predict_args.h", "pht_psis_args.h", "pht_estep_args.h",
            "pht_quantile_args.h", "pht_forecast_args.h", "pht_condition_args.h", "pht_spares_args.h",
-           "host_internal.h", "host_hip.h", "host_lists.h", "host_unif_plan.h"]
+           "pht_wave.h", "pht_unit_walk.h", "pht_condition_draw.inc", "pht_spares_draw.inc", "host_internal.h", "host_hip.h", "host_lists.h", "host_unif_plan.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
 

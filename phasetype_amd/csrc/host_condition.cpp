@@ -113,15 +113,7 @@ extern "C" int pht_ctx_condition(pht_ctx *c, int ndraws, const double *S, const 
     if (clk.mark(0, st)) return -1;
     LlunifTableArgs t;
     if (unif_tables(c, plan, d0, nb, t)) return -1;
-    CondTableArgs f{};
-    f.n = n;
-    f.nd = nb;
-    f.S = t.S;
-    f.meta = t.meta;
-    f.F = c->d_cdF.get();
-    f.fstride = fstride;
-    f.rows = Kcall + 1;
-    HIPCHK(pht_launch_cond_forward(&f, st));
+    if (cond_forward(c, t, c->d_cdF.get(), fstride, Kcall + 1, nb)) return -1;
     if (clk.mark(1, st)) return -1;
     CondArgs a{};
     a.n = n;
@@ -133,7 +125,7 @@ extern "C" int pht_ctx_condition(pht_ctx *c, int ndraws, const double *S, const 
     a.meta = t.meta;
     a.tab = t.tab;
     a.stride = t.stride;
-    a.F = f.F;
+    a.F = c->d_cdF.get();
     a.fstride = fstride;
     a.vec = c->d_cdvec.get() + (size_t)d0 * nvec;
     a.words = c->d_cdwords.get() + (size_t)d0 * nw;

@@ -17,6 +17,7 @@
  *   host_psis.cpp      PSIS-LOO: pht_ctx_loo_begin / _loo / _end (the fills are host_loglik.cpp's)
  *   host_estep.cpp     expected sufficient statistics: pht_ctx_estep, pht_estep_contract
  *   host_quantile.cpp  quantiles and residual-life quantiles: pht_ctx_quantile, pht_quantile_host
+ *   host_fleet.cpp     what the three fleet calls share: the censored-unit list, pht_ctx_forecast_units, validators
  *   host_forecast.cpp  fleet forecasts of the censored units: pht_ctx_forecast, pht_forecast_host
  *   host_condition.cpp fleet condition of the censored units: pht_ctx_condition, pht_condition_host
  *   host_spares.cpp    fleet spares of the censored units: pht_ctx_spares, pht_spares_host
@@ -348,12 +349,14 @@ int unif_stage(pht_ctx *c, const UnifPlan &p, const double *S, const double *s);
 /* the table kernel over the batch [d0, d0 + nb) of the staged plan; t: its
  * arguments (t.S, t.s, t.meta, t.tab are what the analysis' own kernels read) */
 int unif_tables(pht_ctx *c, const UnifPlan &p, int d0, int nb, LlunifTableArgs &t);
+/* the forward tables F [nb][fstride] of the same batch (pht_launch_cond_forward), rows a draw, after unif_tables */
+int cond_forward(pht_ctx *c, const LlunifTableArgs &t, double *F, long fstride, int rows, int nb);
 /* the bodies of pht_ctx_X_ms and pht_ctx_X_grid_cap (bad: the refusal's text after "who: ") */
 int clock_read(const char *who, const pht_ctx *c, const PhaseClock pht_ctx::*clk, float *ms0, float *ms1);
 int grid_cap_set(const char *who, const char *bad, pht_ctx *c, int pht_ctx::*cap, int value);
 
-/* ======================= the censored units (host_forecast.cpp), as the
- * forecast and the condition take them */
+/* ======================= the censored units (host_fleet.cpp), as the
+ * forecast, the condition and the spares take them */
 /* the context's censored units listed (once per pht_ctx_set_obs), at least
  * one and at most max_units */
 int censored_units(pht_ctx *c, const char *who, long max_units);

@@ -17,7 +17,6 @@
 #include <cmath>
 
 #include "host_internal.h"
-#include "pht_condition_args.h"
 #include "pht_loglik_unif_args.h"
 #include "pht_spares.h"
 #include "pht_spares_args.h"
@@ -122,15 +121,7 @@ extern "C" int pht_ctx_spares(pht_ctx *c, int ndraws, const double *S, const dou
     if (clk.mark(0, st)) return -1;
     LlunifTableArgs t;
     if (unif_tables(c, plan, d0, nb, t)) return -1;
-    CondTableArgs f{};
-    f.n = n;
-    f.nd = nb;
-    f.S = t.S;
-    f.meta = t.meta;
-    f.F = c->d_spF.get();
-    f.fstride = fstride;
-    f.rows = Kcall + 1;
-    HIPCHK(pht_launch_cond_forward(&f, st));
+    if (cond_forward(c, t, c->d_spF.get(), fstride, Kcall + 1, nb)) return -1;
     SparesVecArgs v{};
     v.n = n;
     v.nd = nb;
@@ -156,7 +147,7 @@ extern "C" int pht_ctx_spares(pht_ctx *c, int ndraws, const double *S, const dou
     a.meta = t.meta;
     a.tab = t.tab;
     a.stride = t.stride;
-    a.F = f.F;
+    a.F = c->d_spF.get();
     a.fstride = fstride;
     a.vec = v.vec;
     a.words = c->d_spwords.get() + (size_t)d0 * nw;

@@ -2,11 +2,12 @@
  * host_unif.cpp — what the analyses that evaluate draws through the
  * uniformisation table share on the host (pht_ctx_loglik_unif, the PSIS fill,
  * pht_ctx_estep, _quantile, _forecast, _condition): the plan of a call
- * (host_unif_plan.h) staged on the device and its per-batch table launch, the
+ * (host_unif_plan.h) staged on the device and its per-batch table launches, the
  * two-phase device clock, the CU count behind the default grids and the
  * bodies of the pht_ctx_X_ms / pht_ctx_X_grid_cap entry points.
  */
 #include "host_internal.h"
+#include "pht_condition_args.h"
 
 using namespace pht;
 using namespace pht::host;
@@ -42,6 +43,19 @@ int pht::host::unif_tables(pht_ctx *c, const UnifPlan &p, int d0, int nb, Llunif
   t.tab = c->d_llutab.get();
   t.stride = p.stride;
   HIPCHK(pht_launch_llunif_table(&t, c->stream.get()));
+  return 0;
+}
+
+int pht::host::cond_forward(pht_ctx *c, const LlunifTableArgs &t, double *F, long fstride, int rows, int nb) {
+  CondTableArgs f{};
+  f.n = t.n;
+  f.nd = nb;
+  f.S = t.S;
+  f.meta = t.meta;
+  f.F = F;
+  f.fstride = fstride;
+  f.rows = rows;
+  HIPCHK(pht_launch_cond_forward(&f, c->stream.get()));
   return 0;
 }
 

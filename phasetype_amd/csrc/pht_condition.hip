@@ -13,20 +13,17 @@
  * dependent steps.  The table stays in global memory: n (K + 1) doubles a draw,
  * 164 KB at n = 10, K = 2047, more than LDS holds.
  *
- * cond_kernel: pht_forecast.hip's structure — one lane per censored unit over
- * the context's ages (sorted, so neighbouring lanes walk neighbouring k),
- * tiles over a capped grid, the launch's draws taken in passes of as many
- * whole (ax, ac) tables as fit kCondPool doubles, invk[k] and the table rows
- * of the FIRST pass over a unit's window (pht_es_window) read from LDS.  The
- * SECOND pass reads the rows F[k][.] through the caches: the lanes of a wave
- * are at neighbouring k, so a row is read by many lanes at once.  v[n] lives
- * in registers: the kernel is built for n = 3, 5, 10, 15, 20 and once for a
- * runtime n up to 32 (every loop over the phases unrolled to 32 and masked).
- * Lanes past the last unit are masked, never returned early.  Per draw and
- * word: a wave-shuffle sum, one LDS add per wave, one 64-bit atomic per word
- * at the end of the block (nunits = units - nbad is the host's).  A unit's
- * sums and its count live in global memory, [unit][word], read and written by the owning
- * lane once per draw in which the unit is good: in draw order.
+ * cond_kernel: a unit walk (pht_unit_walk.h) over the context's censored units
+ * and their sorted ages.  The FIRST pass over a unit's window (pht_es_window)
+ * reads invk[k] and the table rows from LDS.  The SECOND pass reads the rows
+ * F[k][.] through the caches: the lanes of a wave are at neighbouring k, so a
+ * row is read by many lanes at once.  v[n] lives in registers: the kernel is
+ * built for n = 3, 5, 10, 15, 20 and once for a runtime n up to 32 (every loop
+ * over the phases unrolled to 32 and masked).  Per draw and word: a
+ * wave-shuffle sum, one LDS add per wave, one 64-bit atomic per word at the
+ * end of the block (nunits = units - nbad is the host's).  A unit's sums and
+ * its count live in global memory, [unit][word], read and written by the
+ * owning lane once per draw in which the unit is good: in draw order.
  *
  * LDS at n <= 20: 32 KB of tables, 16 KB of 1 / k, 7 KB of math tables, 2 KB
  * of meta words and 19 KB of block sums (64 draws x 38 words): under 80 KB,
@@ -39,19 +36,13 @@
 #include "pht_condition_args.h"
 #include "pht_kernels.h"
 #include "pht_layout.h"
+#include "pht_unit_walk.h"
 
 namespace pht {
 
 static_assert(kCondMaxH == PHT_CD_MAXH, "the header's limit");
 static_assert(kMaxN == 32, "the header's stack arrays");
 static_assert(kCondBlock % 64 == 0 && kCondBlock >= 64 && kCondBlock <= 1024, "whole waves");
-constexpr int kCondPool = 2 * (PHT_LLU_MAXK + 1); /* doubles of (ax, ac) table per pass */
-
-__device__ __forceinline__ long long cd_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ void __launch_bounds__(64) cond_forward_kernel(const CondTableArgs a) {
   const int d = blockIdx.x, lane = threadIdx.x, n = a.n;
@@ -82,109 +73,82 @@ template <int NT, bool PW>
 __global__ void __launch_bounds__(kCondBlock) cond_kernel(const CondArgs a) {
   constexpr int NV = NT ? NT : kMaxN;       /* length of v */
   constexpr int WL = NV + kCondMaxH + 2;    /* block sums a draw: the words but nunits */
-  __shared__ double stab[kCondPool];
+  __shared__ double stab[kUnitPool];
   __shared__ double sinvk[PHT_LLU_MAXK + 1];
   __shared__ double smeta[kLoglikBatch * PHT_LLU_META];
   __shared__ unsigned long long ssum[kLoglikBatch * WL];
   const int tid = threadIdx.x, nh = a.nh, n = NT ? NT : a.n;
   const int count = (int)a.count, fstride = (int)a.fstride;
   const int nw = pht_cd_nwords(n, nh), nvec = cond_vec_doubles(n, nh);
-  pht_stage_math_tables();
-  for (int k = tid; k <= a.Kmax; k += kCondBlock) sinvk[k] = k ? 1.0 / (double)k : 0.0;
-  for (int k = tid; k < a.nd * PHT_LLU_META; k += kCondBlock) smeta[k] = a.meta[k];
+  unit_stage<kCondBlock>(sinvk, smeta, a.meta, a.nd, a.Kmax);
   for (int k = tid; k < a.nd * WL; k += kCondBlock) ssum[k] = 0ull;
   __syncthreads();
 
-  for (int d0 = 0; d0 < a.nd;) {
-    /* this pass: draws [d0, d1), as many whole tables as fit the pool (the
-     * same count in every lane; a flagged draw takes no room) */
-    int d1 = d0, used = 0;
-    while (d1 < a.nd) {
-      const double *m = smeta + d1 * PHT_LLU_META;
-      const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
-      if (used + need > kCondPool) break;
-      for (int k = tid; k < need; k += kCondBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
-      used += need;
-      d1++;
+  if constexpr (NT == 0) {
+    /* runtime n: unit_walk written out with the body in place (the body in a lambda costs this build 50 to 60
+     * VGPRs and 3 to 4 % of its time) */
+    for (int d0 = 0; d0 < a.nd;) {
+      int d1 = d0, used = 0;
+      while (d1 < a.nd) {
+        const double *m = smeta + d1 * PHT_LLU_META;
+        const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
+        if (used + need > kUnitPool) break;
+        for (int k = tid; k < need; k += kCondBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
+        used += need;
+        d1++;
+      }
+      __syncthreads();
+      for (int base = (int)blockIdx.x * kCondBlock; base < count; base += (int)gridDim.x * kCondBlock) {
+        const int pos = base + tid;
+        const bool live = pos < count;
+        const double c = live ? a.age[pos] : 1.0;
+        double *st = a.state + (size_t)(live ? pos : 0) * (size_t)(n + 2 + nh);
+        double *pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(n + 1 + nh) : nullptr;
+        int off = 0;
+        for (int d = d0; d < d1; d++) {
+          const double *m = smeta + d * PHT_LLU_META;
+          if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) {
+            if (PW && live) {
+              double *pw = pwt + (size_t)d * (size_t)(n + 1 + nh);
+              for (int j = 0; j < n + 1 + nh; j++) pw[j] = NAN;
+            }
+            continue;
+          }
+          const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
+          const double mu = m[PHT_LLU_M_MU], abar = m[PHT_LLU_M_ABAR];
+          const double *tab = stab + off;
+          off += 2 * (K + 1);
+#include "pht_condition_draw.inc"
+        }
+      }
+      d0 = d1;
+      __syncthreads();
     }
-    __syncthreads();
-
-    /* (count <= 2^22: the positions fit an int) */
-    for (int base = (int)blockIdx.x * kCondBlock; base < count; base += (int)gridDim.x * kCondBlock) {
-      const int pos = base + tid;
-      const bool live = pos < count;
-      const double c = live ? a.age[pos] : 1.0;
-      double *st = a.state + (size_t)(live ? pos : 0) * (size_t)(n + 2 + nh); /* this unit's sums (good lanes only) */
-      /* pointwise: this unit's [draw][phi n, MRL, D nh] */
-      double *pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(n + 1 + nh) : nullptr;
-      int off = 0;
-      for (int d = d0; d < d1; d++) {
-        const double *m = smeta + d * PHT_LLU_META;
-        if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) { /* unusable draw: the same for every lane */
+  } else {
+    /* this lane's unit (count <= 2^22: the positions fit an int) */
+    double c;
+    double *st, *pwt;
+    unit_walk<kCondBlock, int>(
+        stab, smeta, a.tab, a.stride, a.nd, a.Kmax, count,
+        [&](int pos, bool live) {
+          c = live ? a.age[pos] : 1.0;
+          st = a.state + (size_t)(live ? pos : 0) * (size_t)(n + 2 + nh); /* this unit's sums (good lanes only) */
+          /* pointwise: this unit's [draw][phi n, MRL, D nh] */
+          pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(n + 1 + nh) : nullptr;
+        },
+        [&](int d, int, bool live) {
           if (PW && live) {
             double *pw = pwt + (size_t)d * (size_t)(n + 1 + nh);
             for (int j = 0; j < n + 1 + nh; j++) pw[j] = NAN;
           }
-          continue;
-        }
-        const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
-        const double mu = m[PHT_LLU_M_MU], abar = m[PHT_LLU_M_ABAR];
-        const double *tab = stab + off;
-        off += 2 * (K + 1);
-        const double *F = a.F + d * fstride;
-        const double *vec = a.vec + d * nvec; /* m[n], r[nh][n], scales[1 + nh] */
-        int bad;
-        pht_es_win_t win;
-        (void)pht_es_window(tab, sinvk, K, mu, abar, c, 1, &bad, &win);
-        const bool good = live && !bad;
-        double v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; j++) v[j] = 0.0;
-        double ml = 0.0;
-        if (good) {
-          pht_cd_phase(F, n, NV, sinvk, &win, v);
-          pht_cd_phi(n, NV, v);
-          ml = pht_cd_dot(n, NV, v, vec);
-        }
-        /* pointwise: this (draw, unit)'s [phi n, MRL, D nh] */
-        double *pw = PW ? pwt + (size_t)d * (size_t)(n + 1 + nh) : nullptr;
-        unsigned long long *sw = ssum + d * WL;
-        /* the phases: word j, the unit's phisum_j, the pointwise value */
-#pragma unroll
-        for (int j = 0; j < NV; j++) {
-          if (j < n) {
-            long long w = good ? pht_cd_fixed(v[j]) : 0;
-            if (good) st[j] = st[j] + v[j];
-            if (PW && live) pw[j] = good ? v[j] : NAN;
-            w = cd_wave_sum(w);
-            if ((tid & 63) == 0) atomicAdd(sw + j, (unsigned long long)w);
-          }
-        }
-        {
-          long long w = good ? pht_cd_fixed_scaled(ml, vec[n + nh * n]) : 0;
-          if (good) st[n] = st[n] + ml;
-          if (PW && live) pw[n] = good ? ml : NAN;
-          w = cd_wave_sum(w);
-          if ((tid & 63) == 0) atomicAdd(sw + pht_cd_w_L(n), (unsigned long long)w);
-        }
-        for (int h = 0; h < nh; h++) {
-          const double dv = good ? pht_cd_dot(n, NV, v, vec + n + h * n) : 0.0;
-          long long w = good ? pht_cd_fixed_scaled(dv, vec[n + nh * n + 1 + h]) : 0;
-          if (good) st[n + 1 + h] = st[n + 1 + h] + dv;
-          if (PW && live) pw[n + 1 + h] = good ? dv : NAN;
-          w = cd_wave_sum(w);
-          if ((tid & 63) == 0) atomicAdd(sw + pht_cd_w_D(n, h), (unsigned long long)w);
-        }
-        {
-          long long w = (live && bad) ? 1 : 0;
-          if (good) st[n + 1 + nh] = st[n + 1 + nh] + 1.0; /* cnt, a whole number below 2^53 */
-          w = cd_wave_sum(w);
-          if ((tid & 63) == 0) atomicAdd(sw + pht_cd_w_nbad(n, nh), (unsigned long long)w);
-        }
-      }
-    }
-    d0 = d1;
-    __syncthreads(); /* every lane is done with this pass's tables */
+        },
+        [&](const UnitDraw &u, int, bool live) {
+          const int d = u.d, K = u.K;
+          const double mu = u.mu, abar = u.abar;
+          const double *tab = u.tab;
+#include "pht_condition_draw.inc"
+        },
+        [](int, bool) {});
   }
   /* the block's sums: word i of draw d (i < nw - 1: nunits is the host's) */
   for (int k = tid; k < a.nd * WL; k += kCondBlock) {

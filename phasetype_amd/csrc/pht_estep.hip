@@ -40,6 +40,7 @@
 #include "pht_kernels.h"
 #include "pht_layout.h"
 #include "pht_loglik_unif_args.h"
+#include "pht_wave.h"
 
 namespace pht {
 
@@ -58,11 +59,6 @@ static_assert(kEstepSkew >= 0 && kEstepSkew <= 63 && (kEstepSkew & (kEstepSkew +
 constexpr int kEstepCells = kMaxN * kMaxN;
 static_assert(kMaxN == 32 && kEstepCells == 1024, "one lane per cell of a 32 x 32 generator");
 
-__device__ __forceinline__ long long es_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ int es_wave_max(int v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
@@ -79,14 +75,14 @@ __device__ __forceinline__ int es_wave_min(int v) {
 __device__ __forceinline__ void es_emit(unsigned long long *shist, int k, long long g, long long t, int cens,
                                         bool hasx, bool hasc, bool lane0) {
   if (hasx) {
-    const long long gs = es_wave_sum(cens ? 0ll : g), ts = es_wave_sum(cens ? 0ll : t);
+    const long long gs = wave_sum(cens ? 0ll : g), ts = wave_sum(cens ? 0ll : t);
     if (lane0 && (gs | ts)) {
       atomicAdd(shist + pht_es_idx(0, k, 0), (unsigned long long)gs);
       atomicAdd(shist + pht_es_idx(0, k, 1), (unsigned long long)ts);
     }
   }
   if (hasc) {
-    const long long gs = es_wave_sum(cens ? g : 0ll), ts = es_wave_sum(cens ? t : 0ll);
+    const long long gs = wave_sum(cens ? g : 0ll), ts = wave_sum(cens ? t : 0ll);
     if (lane0 && (gs | ts)) {
       atomicAdd(shist + pht_es_idx(1, k, 0), (unsigned long long)gs);
       atomicAdd(shist + pht_es_idx(1, k, 1), (unsigned long long)ts);
@@ -140,9 +136,9 @@ __global__ void __launch_bounds__(kEstepBlock) estep_hist_kernel(const EstepHist
           bo = 1;
         }
       }
-      h = es_wave_sum(h);
-      f = es_wave_sum(f);
-      bo = es_wave_sum(bo);
+      h = wave_sum(h);
+      f = wave_sum(f);
+      bo = wave_sum(bo);
       if (lane0) {
         atomicAdd(stot + 0, (unsigned long long)h);
         atomicAdd(stot + 1, (unsigned long long)f);

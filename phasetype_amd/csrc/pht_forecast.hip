@@ -5,22 +5,18 @@
  * pht_loglik_unif.hip's (pht_launch_llunif_table, with the K of the largest
  * age plus the last horizon); one kernel of its own per batch of draws.
  *
- * fcast_kernel: pht_loglik_unif.hip's structure — one lane per censored unit
- * over the context's ages (sorted, so neighbouring lanes walk neighbouring k),
- * tiles over a capped grid, the launch's draws taken in passes of as many
- * whole tables as fit kFcastPool doubles, invk[k] and the table rows read
- * from LDS in the hot loop.  Per (draw, unit) one evaluation at the age, then
- * one per horizon in ascending order (a lane's successive windows overlap);
- * the loop runs j = -1 .. nh - 1 so that all of them share one copy of the
- * evaluator's loops.  Lanes past the last unit are masked, never returned
- * early.  Per (draw, horizon): wave-shuffle sums of (M, V, bad), one LDS add
- * per wave, one 64-bit atomic per word at the end of the block (nunits =
- * units - nbad is the host's).  A unit's qsum and cnt of every horizon stay in
- * registers over the draws of a pass, loaded and stored once per pass; they
- * are updated through a switch on the wave-uniform horizon index, so every
- * register index is a compile-time constant (no scratch).  For that the kernel
- * is built with NH = 4 and NH = 16 state slots a unit (pht_fcast_slots): up to
- * four horizons cost 12 registers of state, not 48.
+ * fcast_kernel: a unit walk (pht_unit_walk.h) over the context's censored
+ * units and their sorted ages.  Per (draw, unit) one evaluation at the age,
+ * then one per horizon in ascending order (a lane's successive windows
+ * overlap); the loop runs j = -1 .. nh - 1 so that all of them share one copy
+ * of the evaluator's loops.  Per (draw, horizon): wave-shuffle sums of (M, V,
+ * bad), one LDS add per wave, one 64-bit atomic per word at the end of the
+ * block (nunits = units - nbad is the host's).  A unit's qsum and cnt of every
+ * horizon stay in registers over the draws of a pass, loaded and stored once
+ * per pass; they are updated through a switch on the wave-uniform horizon
+ * index, so every register index is a compile-time constant (no scratch).  For
+ * that the kernel is built with NH = 4 and NH = 16 state slots a unit
+ * (pht_fcast_slots): up to four horizons cost 12 registers of state, not 48.
  *
  * LDS: 32 KB of tables, 16 KB of 1 / k, 7 KB of math tables, 2 KB of meta
  * words and 20 KB of block sums (64 draws x 16 horizons x (8 + 8 + 4) bytes):
@@ -32,38 +28,24 @@
 #include "pht_forecast_args.h"
 #include "pht_kernels.h"
 #include "pht_layout.h"
+#include "pht_unit_walk.h"
 
 namespace pht {
 
 static_assert(kFcastMaxH == PHT_FC_MAXH && kFcastMaxH == 16, "the header's limit; the switch below lists 16 cases");
 static_assert(kFcastBlock % 64 == 0 && kFcastBlock >= 64 && kFcastBlock <= 1024, "whole waves");
-constexpr int kFcastPool = 2 * (PHT_LLU_MAXK + 1);     /* doubles of table per pass */
 constexpr int kFcastCells = kLoglikBatch * kFcastMaxH; /* (draw, horizon) pairs of a launch */
-
-__device__ __forceinline__ long long fc_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ int fc_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <bool PW, int NH>
 __global__ void __launch_bounds__(kFcastBlock) fcast_kernel(const FcastArgs a) {
-  __shared__ double stab[kFcastPool];
+  __shared__ double stab[kUnitPool];
   __shared__ double sinvk[PHT_LLU_MAXK + 1];
   __shared__ double smeta[kLoglikBatch * PHT_LLU_META];
   __shared__ unsigned long long sM[kFcastCells], sV[kFcastCells];
   __shared__ unsigned sB[kFcastCells];
   __shared__ double sh[kFcastMaxH];
   const int tid = threadIdx.x, nh = a.nh;
-  pht_stage_math_tables();
-  for (int k = tid; k <= a.Kmax; k += kFcastBlock) sinvk[k] = k ? 1.0 / (double)k : 0.0;
-  for (int k = tid; k < a.nd * PHT_LLU_META; k += kFcastBlock) smeta[k] = a.meta[k];
+  unit_stage<kFcastBlock>(sinvk, smeta, a.meta, a.nd, a.Kmax);
   if (tid < nh) sh[tid] = a.h[tid];
   for (int k = tid; k < a.nd * nh; k += kFcastBlock) {
     sM[k] = 0ull;
@@ -72,44 +54,28 @@ __global__ void __launch_bounds__(kFcastBlock) fcast_kernel(const FcastArgs a) {
   }
   __syncthreads();
 
-  for (int d0 = 0; d0 < a.nd;) {
-    /* this pass: draws [d0, d1), as many whole tables as fit the pool (the
-     * same count in every lane; a flagged draw takes no room) */
-    int d1 = d0, used = 0;
-    while (d1 < a.nd) {
-      const double *m = smeta + d1 * PHT_LLU_META;
-      const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
-      if (used + need > kFcastPool) break;
-      for (int k = tid; k < need; k += kFcastBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
-      used += need;
-      d1++;
-    }
-    __syncthreads();
-
-    for (long base = (long)blockIdx.x * kFcastBlock; base < a.count; base += (long)gridDim.x * kFcastBlock) {
-      const long pos = base + tid;
-      const bool live = pos < a.count;
-      const double c = live ? a.age[pos] : 1.0;
-      /* the unit's state: NH slots a unit on the device (the slots past nh stay 0) */
-      double qs[NH];
-      int cn[NH];
+  /* this lane's unit: its age and its state, NH slots a unit on the device (the slots past nh stay 0) */
+  double c;
+  double qs[NH];
+  int cn[NH];
+  unit_walk<kFcastBlock, long>(
+      stab, smeta, a.tab, a.stride, a.nd, a.Kmax, a.count,
+      [&](long pos, bool live) {
+        c = live ? a.age[pos] : 1.0;
 #pragma unroll
-      for (int t = 0; t < NH; t++) {
-        qs[t] = live ? a.qsum[(size_t)pos * NH + t] : 0.0;
-        cn[t] = live ? a.cnt[(size_t)pos * NH + t] : 0;
-      }
-      int off = 0;
-      for (int d = d0; d < d1; d++) {
-        const double *m = smeta + d * PHT_LLU_META;
-        if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) { /* unusable draw: the same for every lane */
-          if (PW && live)
-            for (int j = 0; j < nh; j++) a.q[((size_t)d * (size_t)a.count + (size_t)pos) * nh + j] = NAN;
-          continue;
+        for (int t = 0; t < NH; t++) {
+          qs[t] = live ? a.qsum[(size_t)pos * NH + t] : 0.0;
+          cn[t] = live ? a.cnt[(size_t)pos * NH + t] : 0;
         }
-        const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
-        const double mu = m[PHT_LLU_M_MU], abar = m[PHT_LLU_M_ABAR];
-        const double *tab = stab + off;
-        off += 2 * (K + 1);
+      },
+      [&](int d, long pos, bool live) {
+        if (PW && live)
+          for (int j = 0; j < nh; j++) a.q[((size_t)d * (size_t)a.count + (size_t)pos) * nh + j] = NAN;
+      },
+      [&](const UnitDraw &u, long pos, bool live) {
+        const int d = u.d, K = u.K;
+        const double mu = u.mu, abar = u.abar;
+        const double *tab = u.tab;
         int bad0 = 0;
         double l0 = 0.0;
         for (int j = -1; j < nh; j++) { /* j = -1: the age itself (one copy of the evaluator's loops) */
@@ -147,9 +113,9 @@ __global__ void __launch_bounds__(kFcastBlock) fcast_kernel(const FcastArgs a) {
               break;
           }
           if (PW && live) a.q[((size_t)d * (size_t)a.count + (size_t)pos) * nh + j] = q;
-          mw = fc_wave_sum(mw);
-          vw = fc_wave_sum(vw);
-          bw = fc_wave_sum(bw);
+          mw = wave_sum(mw);
+          vw = wave_sum(vw);
+          bw = wave_sum(bw);
           if ((tid & 63) == 0) {
             const int cell = d * nh + j;
             atomicAdd(sM + cell, (unsigned long long)mw);
@@ -157,18 +123,16 @@ __global__ void __launch_bounds__(kFcastBlock) fcast_kernel(const FcastArgs a) {
             atomicAdd(sB + cell, (unsigned)bw);
           }
         }
-      }
-      if (live) {
+      },
+      [&](long pos, bool live) {
+        if (live) {
 #pragma unroll
-        for (int t = 0; t < NH; t++) {
-          a.qsum[(size_t)pos * NH + t] = qs[t];
-          a.cnt[(size_t)pos * NH + t] = cn[t];
+          for (int t = 0; t < NH; t++) {
+            a.qsum[(size_t)pos * NH + t] = qs[t];
+            a.cnt[(size_t)pos * NH + t] = cn[t];
+          }
         }
-      }
-    }
-    d0 = d1;
-    __syncthreads(); /* every lane is done with this pass's tables */
-  }
+      });
   for (int k = tid; k < a.nd * nh; k += kFcastBlock) {
     unsigned long long *w = a.words + (size_t)k * PHT_FC_WORDS;
     if (sM[k] != 0ull) atomicAdd(w + PHT_FC_W_M, sM[k]);

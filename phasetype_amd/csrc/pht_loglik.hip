@@ -20,16 +20,11 @@
 #include "pht_layout.h"
 #include "pht_loglik.h"
 #include "pht_loglik_args.h"
+#include "pht_wave.h"
 
 namespace pht {
 
 constexpr int kLoglikBlock = 256;
-
-__device__ __forceinline__ long long ll_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <int NT, bool PW>
 __global__ void __launch_bounds__(kLoglikBlock) loglik_kernel(const LoglikArgs a) {
@@ -96,9 +91,9 @@ __global__ void __launch_bounds__(kLoglikBlock) loglik_kernel(const LoglikArgs a
         }
         if (PW) a.pw[(size_t)d * (size_t)a.count + (size_t)pos] = l;
       }
-      h = ll_wave_sum(h);
-      f = ll_wave_sum(f);
-      bo = ll_wave_sum(bo);
+      h = wave_sum(h);
+      f = wave_sum(f);
+      bo = wave_sum(bo);
       if ((tid & 63) == 0) {
         unsigned long long *t = stot + d * PHT_LL_TOT;
         atomicAdd(t + 0, (unsigned long long)h);

@@ -8,18 +8,13 @@
  * shuffle in increasing j (no LDS round trip, no barrier); lane 0 stores
  * (ax_k, ac_k).  K dependent steps.
  *
- * llunif_kernel: pht_loglik.hip's structure — one lane per observation over
- * the context's sorted y, tiles over a capped grid, the WAIC state in
- * registers over the draws of a pass, wave-shuffle sums of (h, f, bad, obs),
- * one LDS add per wave and one 64-bit atomic per word and draw at the end of
- * the block; lanes past the last observation are masked, never returned
- * early.  It does not depend on n.  The hot loop reads invk[k] and the
- * interleaved (ax_k, ac_k) from LDS: the launch's draws are taken in passes of
- * as many whole tables as fit kLlunifPool doubles (one table at the cap
- * K = 2047, six to eight at K = 250 .. 310); the WAIC state is reloaded per
- * pass, the draws stay in order.  With the math tables and invk the block
- * stays under 64 KB, two blocks per CU.  y is sorted, so neighbouring lanes
- * walk neighbouring k.
+ * llunif_kernel: a unit walk (pht_unit_walk.h) over the context's sorted y,
+ * one lane per observation, the WAIC state in registers over the draws of a
+ * pass (reloaded per pass, the draws stay in order), wave-shuffle sums of (h,
+ * f, bad, obs), one LDS add per wave and one 64-bit atomic per word and draw
+ * at the end of the block.  It does not depend on n.  A pass holds one table
+ * at the cap K = 2047, six to eight at K = 250 .. 310.  With the math tables
+ * and invk the block stays under 64 KB, two blocks per CU.
  */
 #include <hip/hip_runtime.h>
 
@@ -27,6 +22,7 @@
 #include "pht_layout.h"
 #include "pht_loglik_unif.h"
 #include "pht_loglik_unif_args.h"
+#include "pht_unit_walk.h"
 
 namespace pht {
 
@@ -41,13 +37,6 @@ static_assert(PHT_LLU_MAXK == kUnifMaxK, "the evaluator's table cap is the sampl
 #endif
 constexpr int kLlunifBlock = PHT_LLUNIF_BLOCK;
 static_assert(kLlunifBlock % 64 == 0 && kLlunifBlock >= 64 && kLlunifBlock <= 1024, "whole waves");
-constexpr int kLlunifPool = 2 * (PHT_LLU_MAXK + 1); /* doubles of table per pass */
-
-__device__ __forceinline__ long long llu_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ void __launch_bounds__(64) llunif_table_kernel(const LlunifTableArgs a) {
   const int d = blockIdx.x, lane = threadIdx.x, n = a.n;
@@ -86,56 +75,41 @@ __global__ void __launch_bounds__(64) llunif_table_kernel(const LlunifTableArgs 
 
 template <bool PW>
 __global__ void __launch_bounds__(kLlunifBlock) llunif_kernel(const LlunifArgs a) {
-  __shared__ double stab[kLlunifPool];
+  __shared__ double stab[kUnitPool];
   __shared__ double sinvk[PHT_LLU_MAXK + 1];
   __shared__ double smeta[kLoglikBatch * PHT_LLU_META];
   __shared__ unsigned long long stot[kLoglikBatch * PHT_LL_TOT];
   const int tid = threadIdx.x;
-  pht_stage_math_tables();
-  for (int k = tid; k <= a.Kmax; k += kLlunifBlock) sinvk[k] = k ? 1.0 / (double)k : 0.0;
-  for (int k = tid; k < a.nd * PHT_LLU_META; k += kLlunifBlock) smeta[k] = a.meta[k];
+  unit_stage<kLlunifBlock>(sinvk, smeta, a.meta, a.nd, a.Kmax);
   for (int k = tid; k < a.nd * PHT_LL_TOT; k += kLlunifBlock) stot[k] = 0ull;
   __syncthreads();
 
-  for (int d0 = 0; d0 < a.nd;) {
-    /* this pass: draws [d0, d1), as many whole tables as fit the pool (the
-     * same count in every lane; a flagged draw takes no room) */
-    int d1 = d0, used = 0;
-    while (d1 < a.nd) {
-      const double *m = smeta + d1 * PHT_LLU_META;
-      const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
-      if (used + need > kLlunifPool) break;
-      for (int k = tid; k < need; k += kLlunifBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
-      used += need;
-      d1++;
-    }
-    __syncthreads();
-
-    for (long base = (long)blockIdx.x * kLlunifBlock; base < a.count; base += (long)gridDim.x * kLlunifBlock) {
-      const long pos = base + tid;
-      const bool live = pos < a.count;
-      const double y = live ? a.y[pos] : 1.0;
-      const int cens = live ? (a.cens[pos] != 0) : 0;
-      pht_waic_t w = {0.0, 0.0, 0.0, 0.0, 0.0, 0};
-      if (a.acc && live) {
-        w.ref = a.w_ref[pos];
-        w.S1 = a.w_S1[pos];
-        w.S2 = a.w_S2[pos];
-        w.m = a.w_m[pos];
-        w.r = a.w_r[pos];
-        w.cnt = a.w_cnt[pos];
-      }
-      int off = 0;
-      for (int d = d0; d < d1; d++) {
-        const double *m = smeta + d * PHT_LLU_META;
-        if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) { /* unusable draw: the same for every lane */
-          if (PW && live) a.pw[(size_t)d * (size_t)a.count + (size_t)pos] = NAN;
-          continue;
+  /* this lane's observation and its WAIC state */
+  double y;
+  int cens;
+  pht_waic_t w;
+  unit_walk<kLlunifBlock, long>(
+      stab, smeta, a.tab, a.stride, a.nd, a.Kmax, a.count,
+      [&](long pos, bool live) {
+        y = live ? a.y[pos] : 1.0;
+        cens = live ? (a.cens[pos] != 0) : 0;
+        w = {0.0, 0.0, 0.0, 0.0, 0.0, 0};
+        if (a.acc && live) {
+          w.ref = a.w_ref[pos];
+          w.S1 = a.w_S1[pos];
+          w.S2 = a.w_S2[pos];
+          w.m = a.w_m[pos];
+          w.r = a.w_r[pos];
+          w.cnt = a.w_cnt[pos];
         }
-        const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
+      },
+      [&](int d, long pos, bool live) {
+        if (PW && live) a.pw[(size_t)d * (size_t)a.count + (size_t)pos] = NAN;
+      },
+      [&](const UnitDraw &u, long pos, bool live) {
+        const int d = u.d;
         int bad, khi;
-        const double l = pht_llu_eval(stab + off, sinvk, K, m[PHT_LLU_M_MU], m[PHT_LLU_M_ABAR], y, cens, &bad, &khi);
-        off += 2 * (K + 1);
+        const double l = pht_llu_eval(u.tab, sinvk, u.K, u.mu, u.abar, y, cens, &bad, &khi);
         long long h = 0, f = 0, bo = 0; /* bo: bad << 32 | obs (a wave adds at most 64 of each) */
         if (live) {
           if (bad) {
@@ -147,9 +121,9 @@ __global__ void __launch_bounds__(kLlunifBlock) llunif_kernel(const LlunifArgs a
           }
           if (PW) a.pw[(size_t)d * (size_t)a.count + (size_t)pos] = l;
         }
-        h = llu_wave_sum(h);
-        f = llu_wave_sum(f);
-        bo = llu_wave_sum(bo);
+        h = wave_sum(h);
+        f = wave_sum(f);
+        bo = wave_sum(bo);
         if ((tid & 63) == 0) {
           unsigned long long *t = stot + d * PHT_LL_TOT;
           atomicAdd(t + 0, (unsigned long long)h);
@@ -157,19 +131,17 @@ __global__ void __launch_bounds__(kLlunifBlock) llunif_kernel(const LlunifArgs a
           atomicAdd(t + 2, (unsigned long long)(bo >> 32));
           atomicAdd(t + 3, (unsigned long long)(bo & 0xffffffffll));
         }
-      }
-      if (a.acc && live) {
-        a.w_ref[pos] = w.ref;
-        a.w_S1[pos] = w.S1;
-        a.w_S2[pos] = w.S2;
-        a.w_m[pos] = w.m;
-        a.w_r[pos] = w.r;
-        a.w_cnt[pos] = w.cnt;
-      }
-    }
-    d0 = d1;
-    __syncthreads(); /* every lane is done with this pass's tables */
-  }
+      },
+      [&](long pos, bool live) {
+        if (a.acc && live) {
+          a.w_ref[pos] = w.ref;
+          a.w_S1[pos] = w.S1;
+          a.w_S2[pos] = w.S2;
+          a.w_m[pos] = w.m;
+          a.w_r[pos] = w.r;
+          a.w_cnt[pos] = w.cnt;
+        }
+      });
   for (int k = tid; k < a.nd * PHT_LL_TOT; k += kLlunifBlock)
     if (stot[k] != 0ull) atomicAdd(a.totals + k, stot[k]);
 }

@@ -26,6 +26,7 @@
 #include "pht_device.h"
 #include "pht_predict.h"
 #include "pht_predict_args.h"
+#include "pht_wave.h"
 
 namespace pht {
 
@@ -44,11 +45,6 @@ static_assert(kPpredBlock % 64 == 0, "whole waves");
 constexpr int kPpredJumps = PHT_PPRED_JUMPS;
 constexpr int kPpredLd = PHT_PRED_MAXN + 1; /* the largest padded leading dimension */
 
-__device__ __forceinline__ long long ppred_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ unsigned long long ppred_wave_min(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
@@ -154,14 +150,14 @@ __global__ void __launch_bounds__(kPpredBlock) ppred_kernel(const PpredArgs a) {
     }
   }
 
-  hy = ppred_wave_sum(hy);
-  fy = ppred_wave_sum(fy);
-  hq = ppred_wave_sum(hq);
-  fq = ppred_wave_sum(fq);
-  njump = ppred_wave_sum(njump);
+  hy = wave_sum(hy);
+  fy = wave_sum(fy);
+  hq = wave_sum(hq);
+  fq = wave_sum(fq);
+  njump = wave_sum(njump);
   /* three counts of at most 2^22 per lane: 64 lanes of each fit 28 bits */
-  const long long c01 = ppred_wave_sum((long long)ndone | ((long long)nbad << 32));
-  const long long c2 = ppred_wave_sum((long long)nsurv);
+  const long long c01 = wave_sum((long long)ndone | ((long long)nbad << 32));
+  const long long c2 = wave_sum((long long)nsurv);
   ymin = ppred_wave_min(ymin);
   ymax = ppred_wave_max(ymax);
   if ((tid & 63) == 0) {

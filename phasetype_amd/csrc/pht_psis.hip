@@ -31,6 +31,7 @@
 
 #include "pht_psis.h"
 #include "pht_psis_args.h"
+#include "pht_wave.h"
 
 namespace pht {
 
@@ -63,12 +64,6 @@ __global__ void __launch_bounds__(kPsisTile *kPsisTileRows) psis_transpose_kerne
 __device__ __forceinline__ double psis_wave_max(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-/* pht_psis_butterfly over the lanes' partial sums */
-__device__ __forceinline__ double psis_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
   return v;
 }
 
@@ -113,7 +108,7 @@ __global__ void __launch_bounds__(64) psis_obs_kernel(const PsisArgs a) {
     ml = psis_wave_max(ml);
     double acc = 0.0;
     for (int d = lane; d < S; d += 64) acc = acc + pht_exp(row[d] - ml);
-    const double lppd = (ml + pht_log(psis_wave_sum(acc))) - pht_log((double)S);
+    const double lppd = (ml + pht_log(wave_sum(acc))) - pht_log((double)S);
 
     int fl = 0, ntie = 0;
     bool smooth = false;
@@ -257,7 +252,7 @@ __global__ void __launch_bounds__(64) psis_obs_kernel(const PsisArgs a) {
         mb = psis_wave_max(mb);
       }
     }
-    const double elpd = (ma + pht_log(psis_wave_sum(pa))) - (mb + pht_log(psis_wave_sum(pb)));
+    const double elpd = (ma + pht_log(wave_sum(pa))) - (mb + pht_log(wave_sum(pb)));
     if (lane == 0) {
       a.elpd[obs] = elpd;
       a.khat[obs] = kh;

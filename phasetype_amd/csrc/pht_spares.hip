@@ -19,18 +19,15 @@
  * Kr dependent steps.  Lane i stores r[.][i] and q[.][i]; the scales' maxima
  * are taken in the header's order (i increasing), the same in every lane.
  *
- * spares_kernel: pht_condition.hip's cond_kernel with other words — one lane
- * per censored unit over the context's sorted ages, tiles over a capped grid,
- * the launch's draws in passes of as many whole (ax, ac) tables as fit
- * kSparesPool doubles, invk[k] and the table rows of the first pass over a
- * unit's window from LDS, the rows F[k][.] of the second pass through the
- * caches, v[n] in registers: built for n = 3, 5, 10, 15, 20 and once for a
- * runtime n up to 32.  Lanes past the last unit are masked, never returned
- * early.  Per draw and word: a wave-shuffle sum, one LDS add per wave, one
- * 64-bit atomic per word at the end of the block (nunits = units - nbad is the
- * host's).  A unit's sums and its count live in global memory, [unit][word],
- * read and written by the owning lane once per draw in which the unit is good:
- * in draw order.
+ * spares_kernel: pht_condition.hip's cond_kernel with other words — a unit
+ * walk (pht_unit_walk.h) over the context's censored units, the first pass
+ * over a unit's window from LDS, the rows F[k][.] of the second pass through
+ * the caches, v[n] in registers: built for n = 3, 5, 10, 15, 20 and once for a
+ * runtime n up to 32.  Per draw and word: a wave-shuffle sum, one LDS add per
+ * wave, one 64-bit atomic per word at the end of the block (nunits = units -
+ * nbad is the host's).  A unit's sums and its count live in global memory,
+ * [unit][word], read and written by the owning lane once per draw in which the
+ * unit is good: in draw order.
  *
  * LDS: 32 KB of tables, 16 KB of 1 / k, 7 KB of math tables, 2 KB of meta
  * words and 16.5 KB of block sums (64 draws x 33 words, whatever n): under
@@ -42,6 +39,7 @@
 #include "pht_layout.h"
 #include "pht_spares.h"
 #include "pht_spares_args.h"
+#include "pht_unit_walk.h"
 
 namespace pht {
 
@@ -49,14 +47,7 @@ static_assert(kSparesMaxH == PHT_CD_MAXH, "the header's limit");
 static_assert(kMaxN == 32, "the header's stack arrays");
 static_assert(2 * kSparesMaxH <= 64, "a step's weights fit one wave");
 static_assert(kSparesBlock % 64 == 0 && kSparesBlock >= 64 && kSparesBlock <= 1024, "whole waves");
-constexpr int kSparesPool = 2 * (PHT_LLU_MAXK + 1); /* doubles of (ax, ac) table per pass */
 constexpr int kSparesWL = 2 * kSparesMaxH + 1;      /* block sums a draw: Delta, V at fixed places, nbad */
-
-__device__ __forceinline__ long long sp_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ void __launch_bounds__(64) spares_vectors_kernel(const SparesVecArgs a) {
   const int d = blockIdx.x, lane = threadIdx.x, n = a.n, nh = a.nh;
@@ -139,103 +130,82 @@ template <int NT, bool PW>
 __global__ void __launch_bounds__(kSparesBlock) spares_kernel(const SparesArgs a) {
   constexpr int NV = NT ? NT : kMaxN; /* length of v */
   constexpr int WL = kSparesWL;
-  __shared__ double stab[kSparesPool];
+  __shared__ double stab[kUnitPool];
   __shared__ double sinvk[PHT_LLU_MAXK + 1];
   __shared__ double smeta[kLoglikBatch * PHT_LLU_META];
   __shared__ unsigned long long ssum[kLoglikBatch * WL];
   const int tid = threadIdx.x, nh = a.nh, n = NT ? NT : a.n;
   const int count = (int)a.count, fstride = (int)a.fstride;
   const int nw = pht_sp_nwords(nh), nvec = spares_vec_doubles(n, nh), ns = 3 * nh + 1;
-  pht_stage_math_tables();
-  for (int k = tid; k <= a.Kmax; k += kSparesBlock) sinvk[k] = k ? 1.0 / (double)k : 0.0;
-  for (int k = tid; k < a.nd * PHT_LLU_META; k += kSparesBlock) smeta[k] = a.meta[k];
+  unit_stage<kSparesBlock>(sinvk, smeta, a.meta, a.nd, a.Kmax);
   for (int k = tid; k < a.nd * WL; k += kSparesBlock) ssum[k] = 0ull;
   __syncthreads();
 
-  for (int d0 = 0; d0 < a.nd;) {
-    /* this pass: draws [d0, d1), as many whole tables as fit the pool (the
-     * same count in every lane; a flagged draw takes no room) */
-    int d1 = d0, used = 0;
-    while (d1 < a.nd) {
-      const double *m = smeta + d1 * PHT_LLU_META;
-      const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
-      if (used + need > kSparesPool) break;
-      for (int k = tid; k < need; k += kSparesBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
-      used += need;
-      d1++;
+  if constexpr (NT == 0) {
+    /* runtime n: unit_walk written out with the body in place (the body in a lambda costs this build 50 to 60
+     * VGPRs and 3 to 4 % of its time) */
+    for (int d0 = 0; d0 < a.nd;) {
+      int d1 = d0, used = 0;
+      while (d1 < a.nd) {
+        const double *m = smeta + d1 * PHT_LLU_META;
+        const int need = (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) ? 0 : 2 * (min((int)m[PHT_LLU_M_K], a.Kmax) + 1);
+        if (used + need > kUnitPool) break;
+        for (int k = tid; k < need; k += kSparesBlock) stab[used + k] = a.tab[(size_t)d1 * a.stride + k];
+        used += need;
+        d1++;
+      }
+      __syncthreads();
+      for (int base = (int)blockIdx.x * kSparesBlock; base < count; base += (int)gridDim.x * kSparesBlock) {
+        const int pos = base + tid;
+        const bool live = pos < count;
+        const double c = live ? a.age[pos] : 1.0;
+        double *st = a.state + (size_t)(live ? pos : 0) * (size_t)ns;
+        double *pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(2 * nh) : nullptr;
+        int off = 0;
+        for (int d = d0; d < d1; d++) {
+          const double *m = smeta + d * PHT_LLU_META;
+          if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) {
+            if (PW && live) {
+              double *pw = pwt + (size_t)d * (size_t)(2 * nh);
+              for (int j = 0; j < 2 * nh; j++) pw[j] = NAN;
+            }
+            continue;
+          }
+          const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
+          const double mu = m[PHT_LLU_M_MU], abar = m[PHT_LLU_M_ABAR];
+          const double *tab = stab + off;
+          off += 2 * (K + 1);
+#include "pht_spares_draw.inc"
+        }
+      }
+      d0 = d1;
+      __syncthreads();
     }
-    __syncthreads();
-
-    /* (count <= 2^22: the positions fit an int) */
-    for (int base = (int)blockIdx.x * kSparesBlock; base < count; base += (int)gridDim.x * kSparesBlock) {
-      const int pos = base + tid;
-      const bool live = pos < count;
-      const double c = live ? a.age[pos] : 1.0;
-      double *st = a.state + (size_t)(live ? pos : 0) * (size_t)ns; /* this unit's sums (good lanes only) */
-      /* pointwise: this unit's [draw][D nh, var nh] */
-      double *pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(2 * nh) : nullptr;
-      int off = 0;
-      for (int d = d0; d < d1; d++) {
-        const double *m = smeta + d * PHT_LLU_META;
-        if (__double_as_longlong(m[PHT_LLU_M_FLAG]) != 0) { /* unusable draw: the same for every lane */
+  } else {
+    /* this lane's unit (count <= 2^22: the positions fit an int) */
+    double c;
+    double *st, *pwt;
+    unit_walk<kSparesBlock, int>(
+        stab, smeta, a.tab, a.stride, a.nd, a.Kmax, count,
+        [&](int pos, bool live) {
+          c = live ? a.age[pos] : 1.0;
+          st = a.state + (size_t)(live ? pos : 0) * (size_t)ns; /* this unit's sums (good lanes only) */
+          /* pointwise: this unit's [draw][D nh, var nh] */
+          pwt = PW ? a.pw + (size_t)(live ? pos : 0) * (size_t)a.nd * (size_t)(2 * nh) : nullptr;
+        },
+        [&](int d, int, bool live) {
           if (PW && live) {
             double *pw = pwt + (size_t)d * (size_t)(2 * nh);
             for (int j = 0; j < 2 * nh; j++) pw[j] = NAN;
           }
-          continue;
-        }
-        const int K = min((int)m[PHT_LLU_M_K], a.Kmax);
-        const double mu = m[PHT_LLU_M_MU], abar = m[PHT_LLU_M_ABAR];
-        const double *tab = stab + off;
-        off += 2 * (K + 1);
-        const double *F = a.F + d * fstride;
-        const double *vec = a.vec + d * nvec; /* r[nh][n], q[nh][n], dscale[nh], vscale[nh] */
-        int bad;
-        pht_es_win_t win;
-        (void)pht_es_window(tab, sinvk, K, mu, abar, c, 1, &bad, &win);
-        const bool good = live && !bad;
-        double v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; j++) v[j] = 0.0;
-        if (good) {
-          pht_cd_phase(F, n, NV, sinvk, &win, v);
-          pht_cd_phi(n, NV, v);
-        }
-        /* pointwise: this (draw, unit)'s [D nh, var nh] */
-        double *pw = PW ? pwt + (size_t)d * (size_t)(2 * nh) : nullptr;
-        unsigned long long *sw = ssum + d * WL;
-        for (int h = 0; h < nh; h++) {
-          const double dv = good ? pht_cd_dot(n, NV, v, vec + h * n) : 0.0;
-          const double qv = good ? pht_cd_dot(n, NV, v, vec + (nh + h) * n) : 0.0;
-          const double vv = pht_sp_var(dv, qv);
-          long long wd = good ? pht_cd_fixed_scaled(dv, vec[2 * nh * n + h]) : 0;
-          long long wv = good ? pht_cd_fixed_scaled(vv, vec[2 * nh * n + nh + h]) : 0;
-          if (good) {
-            st[h] = st[h] + dv;
-            st[nh + h] = st[nh + h] + vv;
-            st[2 * nh + h] = st[2 * nh + h] + dv * dv;
-          }
-          if (PW && live) {
-            pw[h] = good ? dv : NAN;
-            pw[nh + h] = good ? vv : NAN;
-          }
-          wd = sp_wave_sum(wd);
-          wv = sp_wave_sum(wv);
-          if ((tid & 63) == 0) {
-            atomicAdd(sw + h, (unsigned long long)wd);
-            atomicAdd(sw + kSparesMaxH + h, (unsigned long long)wv);
-          }
-        }
-        {
-          long long w = (live && bad) ? 1 : 0;
-          if (good) st[3 * nh] = st[3 * nh] + 1.0; /* cnt, a whole number below 2^53 */
-          w = sp_wave_sum(w);
-          if ((tid & 63) == 0) atomicAdd(sw + 2 * kSparesMaxH, (unsigned long long)w);
-        }
-      }
-    }
-    d0 = d1;
-    __syncthreads(); /* every lane is done with this pass's tables */
+        },
+        [&](const UnitDraw &u, int, bool live) {
+          const int d = u.d, K = u.K;
+          const double mu = u.mu, abar = u.abar;
+          const double *tab = u.tab;
+#include "pht_spares_draw.inc"
+        },
+        [](int, bool) {});
   }
   /* the block's sums: place i of draw d -> word Delta_i, V_{i - 16} or nbad (nunits is the host's) */
   for (int k = tid; k < a.nd * WL; k += kSparesBlock) {
