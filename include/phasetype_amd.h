@@ -277,6 +277,40 @@ int pht_ctx_quantile_ms(pht_ctx *c, float *table_ms, float *search_ms);
 int pht_quantile_host(int n, const double *S, const double *s, int np, const double *probs, double t0, double tmax,
                       double *t_out, double *lo_out, double *hi_out, int *nev_out, unsigned *flags_out);
 
+/* Age-replacement policies (include/pht_replace.h is the whole definition): a
+ * unit is replaced at failure (cost cf) or at age tau (cost cp < cf),
+ * whichever comes first; per draw (S, s) with pi = e_1 the long-run cost rate
+ * g(tau) = (cp + (cf - cp) F(tau)) / M(tau), M the restricted mean life, on a
+ * grid of ages, and per cost pair the age that minimises it (the grid's argmin
+ * refined by a 64-way multisection on the sign of g').  No reference
+ * counterpart, and no observations are needed on the context.
+ *
+ * pht_ctx_replace: ndraws draws as in pht_ctx_loglik_unif, `batch` (1..64) per
+ *   launch; G ages (1..1024), finite, positive, strictly increasing; P cost
+ *   pairs (1..16).  Policy outputs, each ndraws * P (all but t_out and g_out
+ *   may be NULL): t_out the optimal age (+inf with PHT_RP_F_NEVER when running
+ *   to failure costs no more), g_out its cost rate, lo_out and hi_out the final
+ *   bracket, j_out the grid's argmin, nev_out the points evaluated, flags_out
+ *   the PHT_RP_F_* bits.  Per draw (may be NULL): m_out the mean life,
+ *   draw_flags_out as in pht_ctx_loglik_unif with PHT_CD_F_TRAP.  The curve,
+ *   each ndraws * G (may be NULL): lS_out = log Fbar, lf_out = log f, M_out and
+ *   aflags_out the PHT_RP_A_* bits (a flagged age is NaN).  The buffers are the
+ *   context's own: its chain, its WAIC state and the other analyses are not
+ *   affected.
+ * pht_ctx_replace_ms: device time of the last call, the tables with the curve
+ *   and the policies.
+ * pht_replace_host: host only (no GPU), one draw; bit for bit what the device
+ *   computes.  Returns the draw's flag word, < 0 on error. */
+int pht_ctx_replace(pht_ctx *c, int ndraws, const double *S, const double *s, int G, const double *ages, int P,
+                    const double *cp, const double *cf, int batch, double *t_out, double *g_out, double *lo_out,
+                    double *hi_out, int *j_out, int *nev_out, unsigned *flags_out, double *m_out,
+                    int *draw_flags_out, double *lS_out, double *lf_out, double *M_out, unsigned *aflags_out);
+int pht_ctx_replace_ms(pht_ctx *c, float *curve_ms, float *policy_ms);
+int pht_replace_host(int n, const double *S, const double *s, int G, const double *ages, int P, const double *cp,
+                     const double *cf, double *t_out, double *g_out, double *lo_out, double *hi_out, int *j_out,
+                     int *nev_out, unsigned *flags_out, double *m_out, double *lS_out, double *lf_out, double *M_out,
+                     unsigned *aflags_out);
+
 /* Fleet forecasts (include/pht_forecast.h is the whole definition): for every
  * draw (S, s) with pi = e_1, every right-censored observation c_i of the
  * context (a unit still in service at age c_i) and every horizon h_j, the

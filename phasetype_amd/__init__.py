@@ -35,7 +35,11 @@ __all__ = ["load", "LJMA_Gibbs", "phtMCMC", "phtMCMC2", "Sweeper", "gibbs_chains
            "forecast_count_quantiles", "FORECAST_MAX_H", "FORECAST_MAX_UNITS",
            "fleet_condition", "condition_combine", "condition_finalise", "condition_host", "ph_state", "ph_mrl",
            "CONDITION_MAX_H", "CONDITION_MAX_UNITS", "CD_F_TRAP", "CD_F_HCAP",
-           "fleet_spares", "spares_combine", "spares_finalise", "spares_host", "ph_renewal"]
+           "fleet_spares", "spares_combine", "spares_finalise", "spares_host", "ph_renewal",
+           "replace_host", "age_replacement", "ph_rmean", "ph_replacement", "fleet_replacement",
+           "replacement_summary", "replacement_overdue", "REPLACE_MAX_AGES", "REPLACE_MAX_PAIRS",
+           "RP_A_BEYOND", "RP_A_EVAL", "RP_A_DRAW", "RP_F_COST", "RP_F_DRAW", "RP_F_NOAGE", "RP_F_UNREFINED",
+           "RP_F_EDGE", "RP_F_EVAL", "RP_F_NEVER", "RP_F_CAP"]
 
 # R/phtMCMC2.R:66-70; "UNIF" (8) is not a reference method: the opt-in
 # uniformisation sampler (phasetype_amd/csrc/pht_unif.h), lowest precedence
@@ -73,6 +77,7 @@ EXPORTS = [
     "pht_forecast_host",
     "pht_ctx_condition", "pht_ctx_condition_grid_cap", "pht_ctx_condition_ms", "pht_condition_host",
     "pht_ctx_spares", "pht_ctx_spares_grid_cap", "pht_ctx_spares_ms", "pht_spares_host",
+    "pht_ctx_replace", "pht_ctx_replace_ms", "pht_replace_host",
 ]
 
 
@@ -201,6 +206,11 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pht_ctx_spares_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pht_spares_host.argtypes = [C.c_int, _dp, _dp, C.c_long, _dp, C.c_int, _dp, C.c_double, _lp, _dp] + \
         [C.c_void_p] * 6
+    L.pht_ctx_replace.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp,
+                                  _dp, _dp, _ip, _ip, _up, _dp, _ip] + [C.c_void_p] * 4
+    L.pht_ctx_replace_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pht_replace_host.argtypes = [C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                   _up, _dp, _dp, _dp, _dp, _up]
     p, pre = _lapack_path()
     if L.pht_bind_lapack(p.encode(), pre.encode()) != 0:
         raise PhaseTypeError(L.pht_last_error().decode())
@@ -600,6 +610,49 @@ class Sweeper:
             raise _err(self.L)
         self.last_quantile_ms = _ms_pair(self.L.pht_ctx_quantile_ms, self.ctx)
         return dict(t=t, lo=lo, hi=hi, nev=nev, flags=flags, bad_draw=dflags != 0, draw_flags=dflags)
+
+    def replace(self, S_list, s_list, ages, cp, cf, batch: int = 64, pointwise: bool = False):
+        """pht_ctx_replace: age-replacement policies (include/pht_replace.h).  A
+        unit is replaced at failure (cost ``cf``) or at age tau (cost ``cp`` <
+        ``cf``); for each draw (S, s) and each pair the age that minimises the
+        long-run cost rate g(tau) = (cp + (cf - cp) F(tau)) / M(tau): the
+        argmin over ``ages`` (1 .. 1024, positive, strictly increasing),
+        refined by a 64-way multisection on the sign of g'.  No observations
+        are needed.
+
+        Returns ``t`` (the optimal age; inf with RP_F_NEVER where running to
+        failure costs no more), ``g`` (its cost rate), ``lo`` and ``hi`` (the
+        final bracket), ``j`` (the grid's argmin), ``nev`` (points evaluated)
+        and ``flags`` (RP_F_* bits), each [draws, P]; ``m`` (the mean life),
+        ``bad_draw`` and ``draw_flags`` per draw; with ``pointwise`` the curve
+        ``lS`` = log Fbar, ``lf`` = log f, ``M`` (the restricted mean life) and
+        ``age_flags`` (RP_A_* bits; a flagged age is NaN), each [draws, G].
+        ``last_replace_ms`` then holds the device time of the tables with the
+        curve and of the policies."""
+        S_all, s_all, nd = _pack_draws(S_list, s_list, self.n)
+        ages = np.ascontiguousarray(np.atleast_1d(ages), np.float64).reshape(-1)
+        cp = np.ascontiguousarray(np.atleast_1d(cp), np.float64).reshape(-1)
+        cf = np.ascontiguousarray(np.atleast_1d(cf), np.float64).reshape(-1)
+        if len(cp) != len(cf):
+            raise ValueError("cp and cf must have the same length")
+        G, P_ = len(ages), len(cp)
+        out = dict(t=np.zeros((nd, P_)), g=np.zeros((nd, P_)), lo=np.zeros((nd, P_)), hi=np.zeros((nd, P_)),
+                   j=np.zeros((nd, P_), np.int32), nev=np.zeros((nd, P_), np.int32),
+                   flags=np.zeros((nd, P_), np.uint32), m=np.zeros(nd))
+        dflags = np.zeros(nd, np.int32)
+        pw = [None] * 4
+        if pointwise:
+            out.update(lS=np.zeros((nd, G)), lf=np.zeros((nd, G)), M=np.zeros((nd, G)),
+                       age_flags=np.zeros((nd, G), np.uint32))
+            pw = [out[k].ctypes.data_as(C.c_void_p) for k in ("lS", "lf", "M", "age_flags")]
+        if self.L.pht_ctx_replace(self.ctx, nd, S_all.reshape(-1), s_all.reshape(-1), G, ages, P_, cp, cf, int(batch),
+                                  out["t"].reshape(-1), out["g"].reshape(-1), out["lo"].reshape(-1),
+                                  out["hi"].reshape(-1), out["j"].reshape(-1), out["nev"].reshape(-1),
+                                  out["flags"].reshape(-1), out["m"], dflags, *pw) != 0:
+            raise _err(self.L)
+        self.last_replace_ms = _ms_pair(self.L.pht_ctx_replace_ms, self.ctx)
+        out.update(bad_draw=dflags != 0, draw_flags=dflags)
+        return out
 
     def forecast_units(self) -> np.ndarray:
         """pht_ctx_forecast_units: the indices, in the order given to
@@ -1826,6 +1879,227 @@ def ph_renewal(S, s, h, given=0.0, device: int = 0):
         raise ValueError(f"not a usable generator (flag {r['flags'][0]})")
     m, v = r["d"][0, 0].reshape(hh.shape), r["var"][0, 0].reshape(hh.shape)
     return (float(m), float(v)) if hh.ndim == 0 else (m, v)
+
+
+# ------------------------------------------------- age-replacement policies
+# include/pht_replace.h, phasetype_amd/csrc/pht_replace.hip (no reference
+# counterpart): at what age to replace a unit preventively, and what it saves
+RP_A_BEYOND, RP_A_EVAL, RP_A_DRAW = 1, 2, 4
+RP_F_COST, RP_F_DRAW, RP_F_NOAGE, RP_F_UNREFINED, RP_F_EDGE, RP_F_EVAL, RP_F_NEVER, RP_F_CAP = \
+    1, 2, 4, 8, 16, 32, 64, 128
+REPLACE_MAX_AGES, REPLACE_MAX_PAIRS = 1024, 16
+
+
+def replace_host(S, s, ages, cp, cf) -> dict:
+    """pht_replace_host (host only, no GPU): ``Sweeper.replace``'s dict with the
+    curve for one draw (policy arrays [P], curve arrays [G], ``m`` a float);
+    bit for bit what the device computes."""
+    L = load()
+    S = np.asarray(S, np.float64)
+    n = S.shape[0]
+    ages = np.ascontiguousarray(np.atleast_1d(ages), np.float64).reshape(-1)
+    cp = np.ascontiguousarray(np.atleast_1d(cp), np.float64).reshape(-1)
+    cf = np.ascontiguousarray(np.atleast_1d(cf), np.float64).reshape(-1)
+    if len(cp) != len(cf):
+        raise ValueError("cp and cf must have the same length")
+    G, P_ = len(ages), len(cp)
+    out = dict(t=np.zeros(P_), g=np.zeros(P_), lo=np.zeros(P_), hi=np.zeros(P_), j=np.zeros(P_, np.int32),
+               nev=np.zeros(P_, np.int32), flags=np.zeros(P_, np.uint32), lS=np.zeros(G), lf=np.zeros(G),
+               M=np.zeros(G), age_flags=np.zeros(G, np.uint32))
+    m = np.zeros(1)
+    f = L.pht_replace_host(n, np.ascontiguousarray(S.reshape(-1, order="F")),
+                           np.ascontiguousarray(s, np.float64).reshape(-1), G, ages, P_, cp, cf, out["t"], out["g"],
+                           out["lo"], out["hi"], out["j"], out["nev"], out["flags"], m, out["lS"], out["lf"],
+                           out["M"], out["age_flags"])
+    if f < 0:
+        raise _err(L)
+    out.update(m=float(m[0]), bad_draw=f != 0, draw_flags=f)
+    return out
+
+
+def _mean_life(S) -> float:
+    """E[T] of PH(e_1, S) with numpy (NaN where -S cannot be solved): only the
+    default grid of ages is sized by it"""
+    try:
+        S = np.asarray(S, np.float64)
+        return float(np.linalg.solve(-S, np.ones(S.shape[0]))[0])
+    except np.linalg.LinAlgError:
+        return float("nan")
+
+
+def _default_ages(S_list) -> np.ndarray:
+    """64 geometric ages from 0.02 to 8 times the median mean life of the draws"""
+    m = np.array([_mean_life(S) for S in S_list])
+    m = m[np.isfinite(m) & (m > 0)]
+    if not len(m):
+        raise ValueError("no draw has a finite mean life: give ages")
+    return float(np.median(m)) * np.geomspace(0.02, 8.0, 64)
+
+
+def age_replacement(S, s, cp, cf, ages=None, device: int = 0) -> dict:
+    """The age-replacement policy of one law PH(e_1, S): ``Sweeper.replace`` on
+    one draw with the curve, every array without the draws' axis (``cp``,
+    ``cf`` scalars or [P]).  ``ages`` defaults to 64 geometric ages from 0.02
+    to 8 mean lives."""
+    S = np.asarray(S, np.float64)
+    ages = _default_ages([S]) if ages is None else ages
+    sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+    try:
+        r = sw.replace([S], [s], ages, cp, cf, pointwise=True)
+    finally:
+        sw.close()
+    if r["bad_draw"][0]:
+        raise ValueError(f"not a usable generator (flag {r['draw_flags'][0]})")
+    out = {k: v[0] for k, v in r.items()}
+    out["ages"] = np.atleast_1d(np.asarray(ages, np.float64))
+    return out
+
+
+def ph_rmean(S, s, tau, device: int = 0):
+    """The restricted mean life E[min(T, tau)] of PH(e_1, S), the shape of
+    ``tau`` (0 at tau = 0; NaN beyond 1400 / the largest rate).
+    ``Sweeper.replace``'s curve on one draw."""
+    S = np.asarray(S, np.float64)
+    tt = np.asarray(tau, np.float64)
+    flat = tt.reshape(-1)
+    if not np.all(flat >= 0) or not np.all(np.isfinite(flat)):
+        raise ValueError("tau must be finite and non-negative")
+    out = np.zeros(flat.shape)
+    ages, inv = np.unique(flat[flat > 0], return_inverse=True)
+    if len(ages):
+        sw = Sweeper(S.shape[0], METHODS["ECS"], 1, device=device)
+        try:
+            M = []
+            for k in range(0, len(ages), REPLACE_MAX_AGES):
+                r = sw.replace([S], [s], ages[k:k + REPLACE_MAX_AGES], 1.0, 2.0, pointwise=True)
+                if r["bad_draw"][0]:
+                    raise ValueError(f"not a usable generator (flag {r['draw_flags'][0]})")
+                M.append(r["M"][0])
+        finally:
+            sw.close()
+        out[flat > 0] = np.concatenate(M)[inv]
+    out = out.reshape(tt.shape)
+    return float(out) if tt.ndim == 0 else out
+
+
+def replacement_summary(r: dict, ages, cp, cf, band=(.025, .5, .975)) -> dict:
+    """The posterior summary of ``Sweeper.replace``'s dict with the curve (host
+    arithmetic only): what ``ph_replacement`` returns."""
+    ages = np.atleast_1d(np.asarray(ages, np.float64))
+    cp, cf = np.atleast_1d(np.asarray(cp, np.float64)), np.atleast_1d(np.asarray(cf, np.float64))
+    t, g, fl = r["t"], r["g"], r["flags"]
+    nd, P_ = t.shape
+    G = len(ages)
+    flagged = np.isnan(t)
+    never = ((fl & RP_F_NEVER) != 0) & ~flagged
+    edge = ((fl & RP_F_EDGE) != 0) & ~never & ~flagged
+    finite = ~flagged & ~never & ~edge
+    ginf = cf[None, :] / r["m"][:, None]
+    saving = 1.0 - g / ginf
+    bands, sbands = np.full((len(band), P_), np.nan), np.full((len(band), P_), np.nan)
+    for p in range(P_):
+        fin = np.isfinite(t[:, p])
+        if fin.any():
+            bands[:, p] = np.quantile(t[fin, p], band)
+        ok = ~np.isnan(saving[:, p])
+        if ok.any():
+            sbands[:, p] = np.quantile(saving[ok, p], band)
+    # the posterior-mean cost curve over the ages at which every unflagged draw is good
+    use = ~np.asarray(r["bad_draw"], bool)
+    good_age = np.all(r["age_flags"][use] == 0, axis=0) if use.any() else np.zeros(G, bool)
+    gbar = np.full((P_, G), np.nan)
+    if use.any() and good_age.any():
+        F = -np.expm1(r["lS"][use][:, good_age])
+        M = r["M"][use][:, good_age]
+        for p in range(P_):
+            if 0 < cp[p] < cf[p] < np.inf:
+                gbar[p, good_age] = ((cp[p] + (cf[p] - cp[p]) * F) / M).mean(0)
+    age_bayes, g_bayes, evpi = np.full(P_, np.nan), np.full(P_, np.nan), np.full(P_, np.nan)
+    for p in range(P_):
+        if not np.all(np.isnan(gbar[p])):
+            k = int(np.nanargmin(gbar[p]))
+            age_bayes[p], g_bayes[p] = ages[k], gbar[p, k]
+            ok = use & ~np.isnan(g[:, p])
+            if ok.any():
+                evpi[p] = g_bayes[p] - g[ok, p].mean()
+    out = dict(r)
+    out.update(ages=ages, cp=cp, cf=cf, band=bands, saving=saving, saving_band=sbands, n_finite=finite.sum(0),
+               n_never=never.sum(0), n_edge=edge.sum(0), n_flagged=flagged.sum(0), g_inf=ginf, gbar=gbar,
+               n_bad_ages=int((~good_age).sum()), age_bayes=age_bayes, g_bayes=g_bayes,
+               g_inf_bar=ginf[use].mean(0) if use.any() else np.full(P_, np.nan), evpi=evpi)
+    return out
+
+
+def ph_replacement(res, TT_or_T, cp, cf, ages=None, C_=None, n=None, burn: int = 0, thin: int = 1, device: int = 0,
+                   batch: int = 64, collation: str = "C", band=(.025, .5, .975)) -> dict:
+    """Age-replacement policies of a chain (``res`` and ``TT_or_T`` as in
+    ``log_lik``; rows ``burn::thin``; ``cp``, ``cf`` scalars or [P]).
+    ``Sweeper.replace``'s dict with the curve plus, per cost pair: ``band``
+    [len(band), P], the posterior ``band`` quantiles of the optimal age over
+    its finite entries; ``n_finite`` (an interior optimum), ``n_never`` (running
+    to failure costs no more: inf), ``n_edge`` (the cost rate still falls at the
+    last age) and ``n_flagged`` (NaN), which sum to the draws; ``saving`` [draws,
+    P] = 1 - g* / g_inf with ``saving_band``; ``gbar`` [P, G], the posterior
+    mean of the cost curve over the ages at which every unflagged draw is good
+    (NaN elsewhere, ``n_bad_ages`` of them); ``age_bayes`` [P], the argmin of
+    ``gbar``: the age to choose under parameter uncertainty, with its cost rate
+    ``g_bayes`` (compare ``g_inf_bar``, the mean cost rate of running to
+    failure); ``evpi`` [P] = g_bayes - mean(g*), what knowing the parameters
+    would save.  ``ages`` defaults to 64 geometric ages from 0.02 to 8 times
+    the median mean life of the draws."""
+    S_list, s_list, n = _chain_draws(res, TT_or_T, C_, n, collation)
+    S_list, s_list = S_list[int(burn)::int(thin)], s_list[int(burn)::int(thin)]
+    if not S_list:
+        raise ValueError("no rows left after burn / thin")
+    ages = _default_ages(S_list) if ages is None else ages
+    sw = Sweeper(n, METHODS["ECS"], 1, device=device)
+    try:
+        r = sw.replace(S_list, s_list, ages, cp, cf, batch=batch, pointwise=True)
+    finally:
+        sw.close()
+    return replacement_summary(r, ages, cp, cf, band)
+
+
+def replacement_overdue(t, age_bayes, c, band=(.025, .5, .975)) -> dict:
+    """Which units of ages ``c`` are past the optimal age (host arithmetic
+    only): ``t`` [draws, P] the draws' optimal ages (inf: never; NaN: not
+    usable), ``age_bayes`` [P].  Sorted ages and ``searchsorted``: no draws x
+    units matrix."""
+    t, c = np.asarray(t, np.float64), np.asarray(c, np.float64).reshape(-1)
+    nd, P_ = t.shape
+    cs = np.sort(c)
+    p_over = np.full((P_, len(c)), np.nan)
+    n_over = np.full((nd, P_), np.nan)
+    nband = np.full((len(band), P_), np.nan)
+    n_bayes = np.zeros(P_, np.int64)
+    for p in range(P_):
+        ok = ~np.isnan(t[:, p])
+        if ok.any():
+            ts = np.sort(t[ok, p])
+            p_over[p] = np.searchsorted(ts, c, side="right") / float(ok.sum())
+            n_over[ok, p] = len(c) - np.searchsorted(cs, t[ok, p], side="left")
+            nband[:, p] = np.quantile(n_over[ok, p], band)
+        n_bayes[p] = len(c) - np.searchsorted(cs, age_bayes[p], side="left") if not np.isnan(age_bayes[p]) else 0
+    return dict(p_overdue=p_over, n_overdue=n_over, n_overdue_band=nband, n_overdue_bayes=n_bayes)
+
+
+def fleet_replacement(res, x, TT_or_T, censored, cp, cf, ages=None, C_=None, n=None, burn: int = 0, thin: int = 1,
+                      device: int = 0, batch: int = 64, collation: str = "C", band=(.025, .5, .975)) -> dict:
+    """``ph_replacement`` applied to a fleet: of the units of ``x`` still in
+    service (``censored`` != 0, at age x_i), ``p_overdue`` [P, units], the share
+    of usable draws whose optimal age the unit has reached; ``n_overdue``
+    [draws, P], the units past each draw's optimal age (NaN for an unusable
+    draw) with ``n_overdue_band``; ``n_overdue_bayes`` [P], the units past
+    ``age_bayes``; ``unit_index``, the units' positions in ``x``."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    idx = np.nonzero(np.asarray(censored).reshape(-1) != 0)[0]
+    if not len(idx):
+        raise ValueError("no unit in service (censored != 0)")
+    r = ph_replacement(res, TT_or_T, cp, cf, ages=ages, C_=C_, n=n, burn=burn, thin=thin, device=device, batch=batch,
+                       collation=collation, band=band)
+    r.update(replacement_overdue(r["t"], r["age_bayes"], x[idx], band))
+    r["unit_index"] = idx
+    return r
 
 
 # ------------------------------------------- expected statistics, EM fitting

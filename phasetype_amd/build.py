@@ -7,8 +7,9 @@ n, in parallel, + the pht_dispatch.hip launcher), the host runtime / C ABI
 pht_loglik_unif.hip by uniformisation) and the posterior-predictive kernel
 (pht_predict.hip), the PSIS-LOO kernels (pht_psis.hip), the E-step kernels
 (pht_estep.hip), the quantile kernel (pht_quantile.hip), the forecast
-kernel (pht_forecast.hip), the condition kernels (pht_condition.hip) and the
-spares kernels (pht_spares.hip), then one link.  The walk over passes, tiles
+kernel (pht_forecast.hip), the condition kernels (pht_condition.hip), the
+spares kernels (pht_spares.hip) and the replacement kernels
+(pht_replace.hip), then one link.  The walk over passes, tiles
 and draws that four of them share is pht_unit_walk.h, the wave sum pht_wave.h.
 ``-ffp-contract=off`` is required: the device path must reproduce the
 oracle's arithmetic bit for bit (no implicit FMA contraction anywhere).
@@ -44,7 +45,7 @@ UNIT_DEFINES = {5: ("PHT_PHILOX_UNROLL",), 20: ("PHT_PHILOX_UNROLL",),
 # the host runtime, one job per unit (csrc/host_internal.h lists them)
 HOST_UNITS = ("host_r.cpp", "host_params.cpp", "host_ctx.cpp", "host_chains.cpp", "host_rccl.cpp", "host_gibbs.cpp",
               "host_resident.cpp", "host_unif.cpp", "host_loglik.cpp", "host_predict.cpp", "host_psis.cpp", "host_estep.cpp", "host_quantile.cpp",
-              "host_fleet.cpp", "host_forecast.cpp", "host_condition.cpp", "host_spares.cpp")
+              "host_fleet.cpp", "host_forecast.cpp", "host_condition.cpp", "host_spares.cpp", "host_replace.cpp")
 # (source, extra defines, extra device-compile flags) per object; the kernel
 # units first: the long compiles start first
 UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT_FLAGS.get(k, ()))
@@ -71,12 +72,16 @@ UNITS = [("pht_kernels_nt.hip", (f"PHT_NT={k}",) + UNIT_DEFINES.get(k, ()), UNIT
     ("pht_condition.hip", (), ("-mllvm", "-disable-machine-licm")),
     # the fleet spares (include/pht_spares.h), likewise, with the condition's flags: its unit kernel is the
     # condition's with other words
-    ("pht_spares.hip", (), ("-mllvm", "-disable-machine-licm"))] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
+    ("pht_spares.hip", (), ("-mllvm", "-disable-machine-licm")),
+    # the age-replacement policies (include/pht_replace.h), likewise, and without machine LICM for the forecast's
+    # reason (with it the policy kernel spills 6 scalar registers and takes 139 VGPRs against 110)
+    ("pht_replace.hip", (), ("-mllvm", "-disable-machine-licm"))] + [(u, (), ()) for u in HOST_UNITS] + [("rstream.c", (), ())]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["pht_claim.h", "pht_device.h", "pht_env.h", "pht_kernels.h", "pht_kernels_impl.h", "pht_layout.h", "rstream.h",
            "pht_ecs_round.h", "pht_ecs_row.h", "pht_dcs_round.h", "pht_cens_round.h", "pht_unif.h",
            "pht_loglik_args.h", "pht_loglik_unif_args.h", "pht_predict_args.h", "pht_psis_args.h", "pht_estep_args.h",
            "pht_quantile_args.h", "pht_forecast_args.h", "pht_condition_args.h", "pht_spares_args.h",
+           "pht_replace_args.h",
            "pht_wave.h", "pht_unit_walk.h", "pht_condition_draw.inc", "pht_spares_draw.inc", "host_internal.h", "host_hip.h", "host_lists.h", "host_unif_plan.h"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 DEFAULT_DEFINES: tuple = ("PHT_DETMATH_LDS",)
@@ -97,7 +102,7 @@ def inputs() -> list:
                                                           "pht_gamma.h", "pht_eigen.h", "pht_loglik.h",
                                                           "pht_loglik_unif.h", "pht_predict.h", "pht_psis.h",
                                                           "pht_estep.h", "pht_quantile.h", "pht_forecast.h",
-                                                          "pht_condition.h", "pht_spares.h")]
+                                                          "pht_condition.h", "pht_spares.h", "pht_replace.h")]
     deps.append(os.path.abspath(__file__))
     return deps
 

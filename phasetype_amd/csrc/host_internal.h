@@ -21,6 +21,7 @@
  *   host_forecast.cpp  fleet forecasts of the censored units: pht_ctx_forecast, pht_forecast_host
  *   host_condition.cpp fleet condition of the censored units: pht_ctx_condition, pht_condition_host
  *   host_spares.cpp    fleet spares of the censored units: pht_ctx_spares, pht_spares_host
+ *   host_replace.cpp   age-replacement policies: pht_ctx_replace, pht_replace_host
  */
 #ifndef PHT_HOST_INTERNAL_H
 #define PHT_HOST_INTERNAL_H
@@ -315,6 +316,14 @@ struct pht_ctx {
   DevBuf<unsigned long long> d_spwords;
   int sp_grid_cap = 0;
   pht::host::PhaseClock sp_clk;
+  /* pht_ctx_replace (never the quantile's buffers either): a call's ages, cost
+   * pairs, horizons and means, one batch's prefix sums [draw][K + 1], its curve
+   * [lS, lf, M][draw][age] with the policies [t, g, lo, hi][draw][pair] and
+   * the words [age flags][draw][age], [j, nev, flags][draw][pair].  Clock:
+   * the tables with the curve, and the policies */
+  DevBuf<double> d_rpin, d_rpcc, d_rpout;
+  DevBuf<int> d_rpouti;
+  pht::host::PhaseClock rp_clk;
 };
 
 namespace pht {
